@@ -8,10 +8,16 @@ node-sharded, RCCL all-gather of each shard's score rows per batch, the one-GPU 
 `--scaling weak`
 gives every GPU 50k nodes. `--profile la-fit` drops NodeNUMAResource (the C2 plugin set).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
     (rehearsal of the sharded flow on a one-GPU box: N processes on device 0, all-gather over gloo through the
      library's host-callback transport: ... bench.py --gpus N --transport gloo --share-gpu)
+
+A plain run sets up, warms up, times the steps and prints the line (the headline figure and what the library's own
+counters of the timed steps give). `--full` adds what takes runs of its own: the CPU baseline (the oracle on the same
+state) and, on the default one-GPU C3 line, the C5 and Coscheduling sub-objects with their oracle samples.
+`--dump-outputs DIR` writes the placements the last timed step returned, one DIR/<field>.npy (float64) per field of
+the placement records; the workload is seeded, so two builds run with the same arguments compare output for output.
 
 Prints ONE JSON line on rank 0 (value = whole-job pod x node evaluations per second).
 """
@@ -320,6 +326,34 @@ def pmc_summary() -> tuple[dict | None, str | None]:
         return None, None
 
 
+DUMP_CAP_BYTES = (64 << 20) - (64 << 10)   # --dump-outputs: array bytes in all (64 MB less room for the .npy headers)
+
+
+def dump_outputs(dirname: str, out, ext=None) -> dict:
+    """--dump-outputs: the last timed step's placement records (and, C5, its extension records), one
+    <dirname>/<field>.npy per field in float64: node indices, counts and flag words are exact; a score above 2^53
+    would round (the plugin scores are far below; C5's 64-bit reservation uids do round, the same way in every run).
+    A few tens of KB per field at the default 2,048 pods per step; a step large enough to pass 64 MB in all is cut to
+    a fixed seeded sample of its pods (rows.npy holds their indices)."""
+    os.makedirs(dirname, exist_ok=True)
+    recs = [(p, r) for p, r in (("", out), ("ext_", ext)) if r is not None]
+    row_bytes = 8 + sum(8 * int(np.prod(r.dtype[f].shape or (1,))) for _, r in recs for f in r.dtype.names)
+    rows = np.arange(len(out))
+    cap = DUMP_CAP_BYTES // row_bytes
+    if len(rows) > cap:
+        rows = np.sort(np.random.default_rng(20260).choice(len(out), cap, replace=False))
+    written = {}
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    for prefix, rec in recs:
+        for f in rec.dtype.names:
+            if f.startswith("pad"):
+                continue
+            a = np.ascontiguousarray(rec[f][rows]).astype(np.float64)
+            np.save(os.path.join(dirname, f"{prefix}{f}.npy"), a)
+            written[f"{prefix}{f}"] = list(a.shape)
+    return written
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -330,8 +364,13 @@ def main() -> None:
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--pods-per-step", type=int, default=2048)
     ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--full", action="store_true",
+                    help="also the runs beside the headline: the CPU baseline, and the C5 and Coscheduling sub-objects "
+                         "of the default (one-GPU, C3) line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the placements of the last timed step as DIR/<field>.npy (float64), on rank 0")
     ap.add_argument("--cpu-sample-pods", type=int, default=2200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--profile", choices=["c3", "la-fit", "c5"], default="c3",
                     help="c5: 100k nodes, LoadAware + Fit + DeviceShare + Reservation (SURVEY 8(d) C5, see --nodes)")
     ap.add_argument("--sample-pct", type=int, default=None,
@@ -341,8 +380,10 @@ def main() -> None:
     ap.add_argument("--share-gpu", action="store_true", help="every rank on device 0 (gloo rehearsal on one GPU)")
     ap.add_argument("--sync", action="store_true", help="one blocking gs_schedule per step (no submission ahead)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the C5 and Coscheduling sub-objects of the default (one-GPU, C3) line")
+                    help="with --full: skip the C5 and Coscheduling sub-objects of the default (one-GPU, C3) line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -407,9 +448,13 @@ def main() -> None:
         synth.load_ext_into(eng, cluster, ext_args)
         pod_ext = cluster.ext["pod_ext"]
 
+    last_ext = None   # C5: the extension records gs_schedule_ext returned beside the last step's placements
+
     def run(lo, hi):
+        nonlocal last_ext
         if c5:
-            return eng.schedule_ext(pods[lo:hi], pod_ext[lo:hi], seq[lo:hi])[0]
+            out, last_ext = eng.schedule_ext(pods[lo:hi], pod_ext[lo:hi], seq[lo:hi])
+            return out
         return eng.schedule(pods[lo:hi], seq[lo:hi])
 
     pods = cluster.pods
@@ -450,6 +495,9 @@ def main() -> None:
         t = torch.tensor([dt], device="cpu" if gloo else "cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out, last_ext)
 
     st = eng.stats()
     pods_timed = args.steps * P
@@ -509,12 +557,13 @@ def main() -> None:
     }
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and c5:
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if want_cpu and c5:
         r = cpu_baseline_c5(cluster, cfg, ext_args, pods, seq, args.cpu_sample_pods // 4)
         r.pop("placements")
         cpu = {"value": r["evals_per_s"], "unit": "evals/s", "cores": 1, "kind": "port", "pods_per_s": r["pods_per_s"],
                "seconds": r["seconds"], "sample": r["sample"]}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif want_cpu:
         hc = host_cpus()
         threads = min(hc["usable"], 16)
         sample_start = args.warmup * P
@@ -602,7 +651,10 @@ def main() -> None:
                              "slowpath_pods": st["slowpath_pods"]},
             "cpu_baseline": cpu,
         }
-        if world == 1 and args.profile == "c3" and args.sample_pct is None and not args.no_extras:
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "step": args.warmup + args.steps - 1, "dtype": "float64",
+                               "arrays": dumped}
+        if args.full and world == 1 and args.profile == "c3" and args.sample_pct is None and not args.no_extras:
             # the C5 and Coscheduling configurations beside the headline (extra keys; the C3 line above is unchanged)
             del eng
             t_x = time.perf_counter()
