@@ -115,7 +115,7 @@ struct Hdr {             // a pod's level header and list head, one value per la
   int32_t tbv;
 };
 struct Dc {              // a decision before it is recorded (decide_core)
-  int action, end_why;   // 0 commit, 1 FitError, 2 stop before the pod, 3 full-row resolution, 4 wait (diagnostics)
+  int action, end_why;   // 0 commit, 1 FitError, 2 stop before the pod, 3 full-row resolution
   uint32_t winner;
   int M, F, Mclean, Md, Fd;
   int64_t T, jp;
@@ -132,11 +132,6 @@ struct Tag {
 };
 
 __device__ __forceinline__ void sp_sleep() { __builtin_amdgcn_s_sleep(2); }
-__device__ __forceinline__ void sp_prio(uint32_t p) {   // s_setprio takes an immediate
-  if (p == 1) __builtin_amdgcn_s_setprio(1);
-  else if (p == 2) __builtin_amdgcn_s_setprio(2);
-  else if (p == 3) __builtin_amdgcn_s_setprio(3);
-}
 
 // The kernel's LDS, at fixed offsets sized for MAX_BATCH pods whatever the batch: every array is at a link-time
 // constant address and [pod][slot] rows have the constant stride SB, so no register holds a carve-up pointer and
@@ -185,7 +180,6 @@ __shared__ int32_t s_committed, s_hostcut, s_nd, s_endwhy;
 __shared__ int32_t s_snap;        // split: decisions whose slot table and batch-start scores the prep wave may read
 __shared__ int32_t s_prep_done;   // split: pods the prep wave has recorded
 __shared__ int32_t s_reprep;      // split: wave 0 -> prep wave: p + 1 = record pod p again over the exact state
-__shared__ int32_t s_vlock, s_vwm;   // split, shared verification: the verifier's lock, its re-scored frontier
 
 // (s_memtime is a scalar-memory instruction: reading its result waits for every LDS operation and scalar load in flight,
 // so a stamp also closes the latency of the prefetches issued before it. HW_REG_SHADER_CYCLES reads 0 on gfx950.)
@@ -275,7 +269,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     for (int k = 0; k < SP_NRES; ++k) { s_jq_head[k] = 0; s_jq_tail[k] = 0; }
     s_verified = 0; s_rb_req = 0; s_end_at = B; s_vend = -1; s_vcut = 0;
     s_committed = 0; s_hostcut = 0; s_nd = 0;
-    s_snap = 0; s_prep_done = 0; s_reprep = 0; s_vlock = 0; s_vwm = 0;
+    s_snap = 0; s_prep_done = 0; s_reprep = 0;
   }
   __syncthreads();
 
@@ -328,10 +322,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     const uint64_t pend0 = __ballot(lane < nd && !rdy0), pend1 = __ballot(lane + 64 < nd && !rdy1);
     r.pend0 = pend0;
     r.pend1 = pend1;
-    if ((a.dbg & 1u) && (pend0 | pend1)) {   // diagnostics: no speculation, wait for the pending rows
-      r.action = 4;
-      return;
-    }
     SPM(28);   // dirty-slot state (versions, ballots)
     if (want_next && p + 1 < B) load_hdr(p + 1, nh);   // consumed by the next decision
     int sc0 = -1, so0 = -1, sc1 = -1, so1 = -1;
@@ -743,65 +733,9 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     }
     r.slowpath = true;
   };
-  // split pipeline, shared verification (dbg bit 17): the decided pods verified in order by whichever wave holds the
-  // lock — the re-scoring and Reserve waves when they complete a pod's re-scoring, wave 0 while it waits. Same rule
-  // as the verify wave: pod v stands iff every row pending at its decision now scores below its maximum for it (its
-  // feasible ones join the Feasible count); a miss asks wave 0 to roll back to v (s_rb_req).
-  const bool vshare = SPLIT && ((a.dbg >> 17) & 1u);
-  // (dbg bit 19, with 17: the prep wave verifies while it waits for the ring, the re-scoring / Reserve waves do not)
-  const bool vprep = vshare && ((a.dbg >> 19) & 1u);
-  // pods the prep wave may work ahead of wave 0's decisions: 1 + 1 (GS_SPEC_AHEAD=2, dbg bit 18: + 2)
-  const int prep_ahead = ((a.dbg >> 18) & 1u) ? SP_PREPQ : SP_PREPQ - 1;
-  auto verify_try = [&]() {
-    int got = 0;
-    if (lane == 0) {
-      int expect = 0;
-      got = __atomic_compare_exchange_n(&s_vlock, &expect, 1, false, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED) ? 1 : 0;
-    }
-    if (!__builtin_amdgcn_readfirstlane(got)) return;
-    if (!ld_acq(&s_rb_req) && !ld_acq(&s_stop)) {
-      int v = ld_acq(&s_verified), wm = ld_acq(&s_vwm);
-      const int qd = ld_acq(&s_decided);
-      while (wm < qd && ld_acq(&rescored[wm])) ++wm;
-      const int cut_v = ld_acq(&s_cut_at);   // (after the frontier: a cut is published before its pod is re-scored)
-      while (v < qd && v <= wm) {
-        if (cut_v >= 0 && v > cut_v) break;
-        const DecRec& d = dec[v];
-        const uint64_t dp0 = d.pend0, dp1 = d.pend1;
-        const int dM = d.M;
-        int mis = 0, fadd = 0;
-        if ((dp0 >> lane) & 1ull) {
-          const int sc = dsc[v * SB + lane];
-          mis |= sc >= 0 && sc >= dM;
-          fadd += sc >= 0;
-        }
-        if ((dp1 >> lane) & 1ull) {
-          const int sc = dsc[v * SB + 64 + lane];
-          mis |= sc >= 0 && sc >= dM;
-          fadd += sc >= 0;
-        }
-        if (__ballot(mis)) {
-          if (lane == 0) st_rel(&s_rb_req, v + 1);
-          break;
-        }
-        const int F = d.F + wave_sum(fadd);
-        if (lane == 0) final_F[v] = F;
-        ++v;
-      }
-      if (lane == 0) {
-        s_vwm = wm;
-        st_rel(&s_verified, v);
-      }
-    }
-    WAVE_FENCE();
-    if (lane == 0) st_rel(&s_vlock, 0);
-  };
-
   if (wv == 0) {
     // ==================================================== decide ====================================================
     __builtin_amdgcn_s_setprio(3);
-    // decisions ahead of the verifier: SP_LAG (the undo log's depth), or fewer (GS_SPEC_LAG, experiments)
-    const int lag = ((a.dbg >> 12) & 15u) ? (int)min((a.dbg >> 12) & 15u, (uint32_t)SP_LAG) : SP_LAG;
     uint32_t dn0 = 0xffffffffu, dn1 = 0xffffffffu;   // slot s's node in lane s % 64 of dn0 / dn1
     int32_t pv0 = -1, pv1 = -1;                      // slot s's latest decided version (pod index)
     int nd = 0, q = 0, end_at = B, end_why = 0;
@@ -906,7 +840,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         s_snap = v;
         s_prep_done = v;
         s_reprep = 0;
-        s_vwm = v;
         s_parked = 0;
         s_rb_req = 0;
       }
@@ -1132,28 +1065,13 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     while (!err) {
       SPM(2);
       if (SPLIT) {
-        int cut_at;
-        if (vshare) {
-          const v4i32 ctl = ld_ctl();   // rb_req, vend (unused), verified, cut_at
-          if (const int rq = ctl.x) {
-            if (!rollback(rq - 1)) break;
-            continue;
-          }
-          ver = ctl.z;
-          cut_at = ctl.w;
-          // a Reserve that needs the host's cpuset selection ends the batch right after its pod; else every pod
-          // before the end of the decisions verified
-          if (cut_at >= 0 && ver > cut_at) { committed = cut_at + 1; host_cut = true; break; }
-          if (ver == end_at) { committed = ver; break; }
-        } else {
-          cut_at = ld_acq(&s_cut_at);
-          const int vs = verify_step(cut_at);
-          if (vs == 1) {
-            if (!rollback(ver)) break;
-            continue;
-          }
-          if (vs == 2) break;
+        const int cut_at = ld_acq(&s_cut_at);
+        const int vs = verify_step(cut_at);
+        if (vs == 1) {
+          if (!rollback(ver)) break;
+          continue;
         }
+        if (vs == 2) break;
         SPM(55);   // split: verification
         if (ps_slot >= 0) {   // the last fresh slot's batch-start scores, then the snapshot the prep wave reads
           flush_fresh();
@@ -1161,15 +1079,14 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         }
         if (lane == 0 && ld_acq(&s_snap) != q) st_rel(&s_snap, q);
         SPM(27);   // verification, fresh slot's scores
-        if (q >= end_at || q - ver >= lag || cut_at >= 0 || ld_acq(&s_prep_done) <= q || ld_acq(&s_reprep)) {
+        if (q >= end_at || q - ver >= SP_LAG || cut_at >= 0 || ld_acq(&s_prep_done) <= q || ld_acq(&s_reprep)) {
           if (ST) {   // diagnostics: why wave 0 waits (first reason that holds)
-            const int why = q >= end_at ? 0 : q - ver >= lag ? 1 : cut_at >= 0 ? 2 : ld_acq(&s_reprep) ? 3 : 4;
+            const int why = q >= end_at ? 0 : q - ver >= SP_LAG ? 1 : cut_at >= 0 ? 2 : ld_acq(&s_reprep) ? 3 : 4;
             st_acc[56 + why] += 1;
           }
           if (++spins > SP_SPIN_LIMIT) { err = true; err_code = 2; break; }
           if (const int we = ld_acq(&s_werr)) { err = true; err_code = we; break; }
-          if (vshare) verify_try();
-          else __builtin_amdgcn_s_sleep(1);
+          __builtin_amdgcn_s_sleep(1);
           if (q >= end_at) SPM(23);   // waiting at the batch's end
           continue;
         }
@@ -1211,7 +1128,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       }
       SPM(27);   // rollback / batch-end checks
       // ------------------------------------------------ decide pod q
-      if (q >= end_at || q - ctl.z >= lag || ctl.w >= 0) {
+      if (q >= end_at || q - ctl.z >= SP_LAG || ctl.w >= 0) {
         if (++spins > SP_SPIN_LIMIT) { err = true; err_code = 2; break; }
         if (const int we = ld_acq(&s_werr)) { err = true; err_code = we; break; }
         sp_sleep();
@@ -1224,11 +1141,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       const Hdr h = nh;
       Dc r;
       decide_core(p, h, nh, true, flush_fresh, nd, dn0, dn1, pv0, pv1, Tag<false>{}, r);
-      if (r.action == 4) {   // diagnostics (no speculation): wait for the pending rows
-        if (++spins > SP_SPIN_LIMIT) { err = true; err_code = 3; break; }
-        sp_sleep();
-        continue;
-      }
       const bool full_row = r.action == 3;
       if (ST) st_acc[10] += full_row ? 1 : 0;
       if (full_row) {
@@ -1299,15 +1211,14 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         p = rq - 1;
         wait = ld_acq(&s_snap) != p;
       } else {
-        wait = pn >= B || pn >= ld_acq(&s_decided) + prep_ahead;
+        wait = pn >= B || pn >= ld_acq(&s_decided) + SP_PREPQ - 1;
       }
       if (wait) {
         if (++spins > SP_SPIN_LIMIT) {
           if (lane == 0) __atomic_store_n(&s_werr, 10, __ATOMIC_RELEASE);
           break;
         }
-        if (vprep) verify_try();   // its idle time: the decided pods' verification
-        else if (pn >= B && !rq) sp_sleep();
+        if (pn >= B && !rq) sp_sleep();
         else __builtin_amdgcn_s_sleep(1);
         SPM(2);
         continue;
@@ -1373,7 +1284,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     // batch-start score was unknown scored below it at batch start); the rows it excluded that are feasible join its
     // Feasible count. A miss asks wave 0 to roll back to v. Verifying v needs the re-scoring of every pod before it
     // (rescored[]), which also means their Reserves (and batch-start jobs) are complete.
-    sp_prio((a.dbg >> 8) & 3u);
     int v = 0, wm = 0;
     uint32_t spins = 0;
     for (;;) {
@@ -1453,7 +1363,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
   } else if (sp_reserve_index(wv) >= 0) {
     // =================================================== Reserve ===================================================
     const int wr = sp_reserve_index(wv);   // this wave's pods: q % SP_NRES == wr
-    sp_prio((a.dbg >> 4) & 3u);
     uint64_t* s_cpuset_w = s_cpuset[wr];
     int32_t& s_aff_w = s_aff[wr];
     Job* jq = jobq + wr * SP_JOBQ;
@@ -1539,7 +1448,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
           __atomic_store_n(&resv[q], 1, __ATOMIC_RELEASE);
         }
         WAVE_FENCE();
-        if (vshare && !vprep) verify_try();
         q += SP_NRES;
         continue;
       }
@@ -1708,7 +1616,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       WAVE_FENCE();
       if (lane == 0) __atomic_store_n(&resv[q], 1, __ATOMIC_RELEASE);
       WAVE_FENCE();
-      if (vshare && !vprep && njobs == 0) verify_try();
       q += SP_NRES;
       SPM(5);
     }
@@ -1716,7 +1623,6 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     // ============================================== re-scoring jobs ==============================================
     uint32_t spins = 0;
     const int ri = SPLIT ? wv - SP_RS0 : sp_rescore_index(wv);   // split: waves 4-7
-    sp_prio((a.dbg >> 6) & 3u);
     int ring = ri % SP_NRES;
     for (;;) {
       if (ld_acq(&s_stop)) {
@@ -1813,17 +1719,13 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       }
       if (q2 < B) dsc[q2 * SB + jb.slot] = (int16_t)row_score(rr, pods(q2), a.pf, m, &tab);
       WAVE_FENCE();
-      int fin = 0;
       if (lane == 0) {
         if (__atomic_fetch_sub(&jobs_left[jb.q], 1, __ATOMIC_ACQ_REL) == 1)
           __atomic_store_n(&done_ver[jb.slot], jb.q, __ATOMIC_RELEASE);
-        if (__atomic_fetch_sub(&jobs_all[jb.q], 1, __ATOMIC_ACQ_REL) == 1) {
+        if (__atomic_fetch_sub(&jobs_all[jb.q], 1, __ATOMIC_ACQ_REL) == 1)
           __atomic_store_n(&rescored[jb.q], 1, __ATOMIC_RELEASE);
-          fin = 1;
-        }
       }
       WAVE_FENCE();
-      if (vshare && !vprep && __builtin_amdgcn_readfirstlane(fin)) verify_try();
       if (ST) st_acc[10] += 1;
       SPM(7);
     }
@@ -1880,33 +1782,15 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
   }
 }
 
-// With an exclusive commit CU the workgroup declares the CU's whole LDS, and the kernels that run beside it (the
-// next batch's eval pass) declare a few bytes (eval_lds_bytes), so none of their waves is placed on the commit's CU.
-template <bool STAMPS, bool SPLIT>
-static size_t spec_launch_bytes(int npods) {
-  if (!commit_cu_exclusive()) return spec_smem_bytes(npods);
-  static const size_t dyn = [] {
-    hipFuncAttributes fa{};
-    size_t st = 0;
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(commit_spec_kernel<STAMPS, SPLIT>)) == hipSuccess)
-      st = fa.sharedSizeBytes;   // the variant's static LDS
-    return std::max(spec_smem_bytes(MAX_BATCH), (size_t)LDS_PER_CU - st);
-  }();
-  return dyn;
-}
-
 template <bool STAMPS, bool SPLIT>
 static void spec_launch(const CommitArgs& a, hipStream_t st) {
-  const size_t bytes = spec_launch_bytes<STAMPS, SPLIT>(a.npods);
-  hipLaunchKernelGGL((commit_spec_kernel<STAMPS, SPLIT>), dim3(1), dim3(SP_THREADS), bytes, st, a);
+  hipLaunchKernelGGL((commit_spec_kernel<STAMPS, SPLIT>), dim3(1), dim3(SP_THREADS), spec_smem_bytes(a.npods), st, a);
 }
 
 hipError_t launch_commit_spec(const CommitArgs& a, hipStream_t st) {
-  // the split pipeline (GS_SPEC_SPLIT, dbg bit 16): one shard, speculation on
-  // and batches of GS_SPEC_SPLIT_MINB pods or more (default 32): a short batch has no selection to hide behind the
-  // prep wave, only its start-up
-  static const int min_b = getenv("GS_SPEC_SPLIT_MINB") ? atoi(getenv("GS_SPEC_SPLIT_MINB")) : 32;
-  const bool split = ((a.dbg >> 16) & 1u) && a.nranks <= 1 && !(a.dbg & 1u) && a.npods >= min_b;
+  // the split pipeline: one shard and batches of 32 pods or more (a short batch has no selection to hide behind the
+  // prep wave, only its start-up)
+  const bool split = a.nranks <= 1 && a.npods >= 32;
   if (a.stamps) {
     if (split) spec_launch<true, true>(a, st);
     else spec_launch<true, false>(a, st);
@@ -1920,7 +1804,7 @@ hipError_t launch_commit_spec(const CommitArgs& a, hipStream_t st) {
 template <bool STAMPS, bool SPLIT>
 static hipError_t spec_attr() {
   return hipFuncSetAttribute(reinterpret_cast<const void*>(commit_spec_kernel<STAMPS, SPLIT>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_launch_bytes<STAMPS, SPLIT>(MAX_BATCH));
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_smem_bytes(MAX_BATCH));
 }
 
 hipError_t set_commit_spec_attributes() {

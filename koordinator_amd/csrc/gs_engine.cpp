@@ -339,12 +339,7 @@ struct Where {
 // blocking synchronisation. Several processes sharing one GPU (the C4 rehearsal) showed a rank parked for 10-100 s
 // inside hipStreamSynchronize / hipEventSynchronize while every stream and event of that rank had long completed (the
 // watchdog's queries), i.e. a lost wake-up of the blocking wait. A poll sees the completion at once;
-// bounded: past GS_WAIT_LIMIT_S (default 600 s) the call fails with GS_EDEVICE naming the wait. GS_WAIT_BLOCKING=1:
-// HIP's blocking calls (experiments).
-bool wait_blocking() {
-  static const bool b = getenv("GS_WAIT_BLOCKING") && getenv("GS_WAIT_BLOCKING")[0] == '1';
-  return b;
-}
+// bounded: past GS_WAIT_LIMIT_S (default 600 s) the call fails with GS_EDEVICE naming the wait.
 template <class Query>
 hipError_t poll_until(Query&& query, double limit_s) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -364,15 +359,13 @@ hipError_t poll_until(Query&& query, double limit_s) {
   }
 }
 double wait_limit_s() {
-  static const double lim = getenv("GS_WAIT_LIMIT_S") ? atof(getenv("GS_WAIT_LIMIT_S")) : 600.0;
+  static const double lim = env_num("GS_WAIT_LIMIT_S", 600.0);
   return lim > 0 ? lim : 600.0;
 }
 hipError_t host_wait_event(hipEvent_t ev) {
-  if (wait_blocking()) return hipEventSynchronize(ev);
   return poll_until([&] { return hipEventQuery(ev); }, wait_limit_s());
 }
 hipError_t host_wait_stream(hipStream_t st) {
-  if (wait_blocking()) return hipStreamSynchronize(st);
   return poll_until([&] { return hipStreamQuery(st); }, wait_limit_s());
 }
 
@@ -952,7 +945,7 @@ int exchange(gs_ctx* c, uint32_t site, uint8_t* d_send, uint8_t* d_recv, size_t 
     return GS_OK;
   } else if (c->lg) {
     gs_local_group& g = *c->lg;
-    static const double limit = getenv("GS_LOCAL_WAIT_S") ? atof(getenv("GS_LOCAL_WAIT_S")) : 60.0;
+    static const double limit = env_num("GS_LOCAL_WAIT_S", 60.0);
     HIP_TRY(c, launch_write_tag(d_send + bytes - sizeof(XTag), tag, xs));
     if (c->x_pending * 2 + 2 > (int)c->x_ev.size()) {
       for (int k = 0; k < 2; ++k) {
@@ -1181,7 +1174,7 @@ int compute_profile(gs_ctx* c) {
 }
 
 // GS_XCHG=levels (read at every comm init): the per-shard candidate levels instead of the score rows
-bool xchg_levels() { return getenv("GS_XCHG") && std::strcmp(getenv("GS_XCHG"), "levels") == 0; }
+bool xchg_levels() { const char* x = env_str("GS_XCHG"); return x && std::strcmp(x, "levels") == 0; }
 
 void set_shard(gs_ctx* c) {
   uint32_t per = (c->N + c->nranks - 1) / c->nranks;
@@ -1237,7 +1230,7 @@ int alloc_exchange(gs_ctx* c) {
   }
   if (!c->d_xsmall) HIP_TRY(c, hipMalloc(&c->d_xsmall, XSMALL * (1 + MAX_RANKS)));
   if (!c->h_xsmall) HIP_TRY(c, hipHostMalloc(&c->h_xsmall, XSMALL * MAX_RANKS, hipHostMallocDefault));
-  if (const char* sk = getenv("GS_DEBUG_XCHG_SKEW")) {   // "rank:batch" (tests of the sequence check)
+  if (const char* sk = env_str("GS_DEBUG_XCHG_SKEW")) {   // "rank:batch" (tests of the sequence check)
     long r = -1;
     unsigned long long b = 0;
     if (sscanf(sk, "%ld:%llu", &r, &b) == 2) { c->dbg_xskew_rank = r; c->dbg_xskew_batch = b; }
@@ -1261,20 +1254,20 @@ constexpr size_t COMMITTED_BYTES = 32;   // committed[0..7] (the commit kernels 
 
 // The candidate levels of a one-shard pass without node sampling are built on st_ev right after the eval pass (beside
 // the previous batch's commit, on the stale rows it lands on), then fixed up on st once that commit is done
-// (GS_FUSED_PATCH=0, the separate patch kernel: not overlapped)
-// A batch with no speculative pass before it, of at most GS_DIRECT_B pods (default 32; 0: none), on one shard: its
+// A batch with no speculative pass before it, of at most SHORT_BATCH pods, on one shard: its
 // upload, eval pass and levels go on st in order instead of through st_ev. st_ev then waits for that eval pass and its
 // levels (launch_batch): a speculative pass enqueued after it on st_ev shares the NUMA slab, st2 and the fork / join
 // events with it, so it starts only once they are done. Short runs (the plain pods between C5's extension pods) lose
 // two queue hops per batch.
+// SHORT_BATCH: a batch of fewer pods is short (the host waits on each one): it is read back in order on st and, when
+// direct, untimed; a batch of up to SHORT_BATCH pods may run direct.
+constexpr int SHORT_BATCH = 32;
 bool direct_batch(const gs_ctx* c, int b, bool speculative) {
-  static const int max_b = getenv("GS_DIRECT_B") ? atoi(getenv("GS_DIRECT_B")) : 32;
-  return !speculative && b <= max_b && lvl_ranks(c) == 1;
+  return !speculative && b <= SHORT_BATCH && lvl_ranks(c) == 1;
 }
 
 bool cand_overlapped(const gs_ctx* c) {
-  static const bool separate = getenv("GS_FUSED_PATCH") && getenv("GS_FUSED_PATCH")[0] == '0';
-  return c->cand_overlap && lvl_ranks(c) == 1 && !c->window_k && c->d_lst && !separate;
+  return c->cand_overlap && lvl_ranks(c) == 1 && !c->window_k && c->d_lst;
 }
 
 CommitArgs commit_args(gs_ctx* c, int b) {
@@ -1306,20 +1299,6 @@ CommitArgs commit_args(gs_ctx* c, int b) {
   a.window_k = c->window_k;
   a.start = c->next_start;
   a.nnodes = c->N;
-  static const bool nospec = getenv("GS_SPEC_WAIT") && getenv("GS_SPEC_WAIT")[0] == '1';
-  // GS_SPEC_PRIO (experiments): issue priorities of the roles, bits 4-5 Reserve, 6-7 re-scoring, 8-9 verify
-  static const uint32_t prio = getenv("GS_SPEC_PRIO") ? (uint32_t)strtoul(getenv("GS_SPEC_PRIO"), nullptr, 0) & 0x3f0u : 0u;
-  // GS_SPEC_LAG (experiments): decisions ahead of the verifier, 1..12 (bits 12-15; 0: the kernel's SP_LAG)
-  static const uint32_t lag = getenv("GS_SPEC_LAG") ? (uint32_t)std::min(12L, std::max(0L, atol(getenv("GS_SPEC_LAG")))) : 0u;
-  // the split selector (one shard; a prep wave decides ahead over a snapshot, wave 0 applies the landings after it),
-  // bit 16: the default (GS_SPEC_SPLIT=0: the single selector wave); GS_SPEC_SPLIT=2 (experiments): and the decided
-  // pods verified by the re-scoring / Reserve waves (bit 17)
-  static const int split = getenv("GS_SPEC_SPLIT") ? atoi(getenv("GS_SPEC_SPLIT")) : 1;
-  // GS_SPEC_AHEAD=2 (experiments): the prep wave may run two pods ahead (bit 18)
-  static const bool ahead2 = getenv("GS_SPEC_AHEAD") && getenv("GS_SPEC_AHEAD")[0] == '2';
-  // GS_SPEC_SPLIT=3 (experiments): shared verification by the prep wave while it waits (bits 17 and 19)
-  a.dbg = (nospec ? 1u : 0u) | prio | lag << 12 | (split >= 1 ? 1u << 16 : 0u) | (split >= 2 ? 1u << 17 : 0u) |
-          (ahead2 ? 1u << 18 : 0u) | (split >= 3 ? 1u << 19 : 0u);
   a.tb = c->d_tb;
   // (score rows: the batch slot's verdict of unpack_scores_kernel; levels: merge_levels_kernel's)
   a.xerr = c->sgather ? c->d_xerr + (XERR_BYTES / 4) * c->cur_slot : c->nranks > 1 ? c->d_xerr : nullptr;
@@ -1332,7 +1311,6 @@ CommitArgs commit_args(gs_ctx* c, int b) {
 // before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel); its commit
 // kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
 int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev_out = nullptr, int prev_b = 0) {
-  static const bool separate = getenv("GS_FUSED_PATCH") && getenv("GS_FUSED_PATCH")[0] == '0';
   const bool ovl = cand_overlapped(c);
   uint8_t* lblk = ovl ? c->d_lst : c->d_xchg_send;
   uint32_t* d_lists = reinterpret_cast<uint32_t*>(lblk);
@@ -1356,8 +1334,7 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
       HIP_TRY(c, hipMalloc(&c->d_numa_idx, 4 * idx.size()));
       HIP_TRY(c, hipMemcpy(c->d_numa_idx, idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
     }
-    static const bool no_slab = getenv("GS_NUMA_SLAB") && getenv("GS_NUMA_SLAB")[0] == '0';
-    if (!no_slab && c->numa_n > c->slab_cap) {   // columns of numa_n entries (rounded), the mirror's numbering
+    if (c->numa_n > c->slab_cap) {   // columns of numa_n entries (rounded), the mirror's numbering
       HIP_TRY(c, host_wait_stream(c->st_ev));
       if (c->slab_mv.i64) (void)hipFree(c->slab_mv.i64);
       if (c->slab_mv.i32) (void)hipFree(c->slab_mv.i32);
@@ -1375,11 +1352,14 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
   // a short batch with no pass beside it: upload, eval and levels in order on st (no queue hops)
   const bool direct = direct_batch(c, b, prev != nullptr);
   hipStream_t se = direct ? c->st : c->st_ev;
+  // full batches: readback on its own stream, so that the speculative next batch's patch / cand start right after the
+  // commit (the slot's buffers are rewritten only after finish_batch has waited for ev[5]). Short batches (the host
+  // waits on each one) keep it in order on st: the extra queue hop costs more than it hides there.
+  hipStream_t rb = b >= SHORT_BATCH ? c->st_rb : c->st;
   // A direct batch read back on st records no timing events: three HIP calls less per short plain run (C5 at 100k nodes,
   // medians of 7 alternations: 23.6k against 21.8k pods/s); its eval and levels intervals are not counted in the stats,
-  // the commit's comes from the kernel. GS_DIRECT_TIMING=1: timed as the other batches.
-  static const bool direct_untimed = !(getenv("GS_DIRECT_TIMING") && getenv("GS_DIRECT_TIMING")[0] == '1');
-  const bool untimed = direct_untimed && direct && b < 32;
+  // the commit's comes from the kernel. (st_rb waits on ev[4]: a batch read back there is always timed.)
+  const bool untimed = direct && rb == c->st;
   c->slot[c->cur_slot].untimed = untimed;
   if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[0], se));
   if (c->sgather) {
@@ -1426,8 +1406,8 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
   }
   // the rows the previous batch landed on, re-evaluated on their committed state: inside cand_kernel (block k patches
   // pod k's row before its histogram; one launch less on the commit chain), or by patch_kernel under node sampling
-  // (no candidate levels) or GS_FUSED_PATCH=0
-  const bool fused = prev && prev_b > 0 && !c->window_k && !separate;
+  // (no candidate levels)
+  const bool fused = prev && prev_b > 0 && !c->window_k;
   if (!ovl && prev && !fused)
     HIP_TRY(c, launch_patch(c->mv, c->d_pods, b, c->pf, c->n0, c->n1, c->d_S, c->ld, prod_cols, c->d_aff, prev_out,
                             prev, prev_b, c->st));
@@ -1450,25 +1430,12 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
   ++c->xbatch;
   HIP_TRY(c, launch_commit(a, c->st));
   if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[4], c->st));
-  // full batches: readback on its own stream, so that the speculative next batch's patch / cand start right after the
-  // commit (the slot's buffers are rewritten only after finish_batch has waited for ev[5]). Short batches (the host
-  // waits on each one) keep it in order on st: the extra queue hop costs more than it hides there.
-  hipStream_t rb = b >= 32 ? c->st_rb : c->st;
   if (rb != c->st) HIP_TRY(c, hipStreamWaitEvent(rb, c->ev[4], 0));
   // Two copies, not one over the adjacent committed words and placements: with one merged copy, 4 processes sharing the
-  // GPU (the C4 rehearsal) stalled for 10-100 s at a time, every rank's commit and next eval pass pending (DESIGN §8;
-  // GS_MERGE_RB=1 restores the merged copy for that experiment)
-  // A direct batch reads back in two copies as well: the merged form measured within noise there and its
-  // stall with several processes on one GPU is not understood (GS_DIRECT_MERGE_RB=1, experiments: one copy)
-  static const bool merge_rb = getenv("GS_MERGE_RB") && getenv("GS_MERGE_RB")[0] == '1';
-  static const bool merge_direct = getenv("GS_DIRECT_MERGE_RB") && getenv("GS_DIRECT_MERGE_RB")[0] == '1';
-  if (merge_rb || (direct && merge_direct && rb == c->st)) {
-    HIP_TRY(c, hipMemcpyAsync(c->h_committed, c->d_committed, COMMITTED_BYTES + sizeof(PlacementDev) * b,
-                              hipMemcpyDeviceToHost, rb));
-  } else {
-    HIP_TRY(c, hipMemcpyAsync(c->h_committed, c->d_committed, COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
-    HIP_TRY(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
-  }
+  // GPU (the C4 rehearsal) stalled for 10-100 s at a time, every rank's commit and next eval pass pending;
+  // for a direct batch the merged form measured within noise
+  HIP_TRY(c, hipMemcpyAsync(c->h_committed, c->d_committed, COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
+  HIP_TRY(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
   HIP_TRY(c, hipEventRecord(c->ev[5], rb));
   return GS_OK;
 }
@@ -1582,7 +1549,7 @@ int finish_batch(gs_ctx* c, int b, bool clobbered, int* committed_out) {
   flush_exchange_times(c);
   if (committed < b) {
     c->stats.cuts += 1;
-    static const bool dbg = getenv("GS_DEBUG_CUTS") && getenv("GS_DEBUG_CUTS")[0] == '1';
+    static const bool dbg = env_on("GS_DEBUG_CUTS");
     if (dbg) {
       const PlacementDev& x = c->h_out[committed];
       fprintf(stderr, "gpuscore: batch of %d ended after %d pods (code %#x) [%d run %u M %lld Mc %lld Md %lld T %u Tc %d new %u old %u jp %lld nd %lld pend %lld]\n",
@@ -1966,7 +1933,7 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
   const size_t in_bytes = nrec ? c->xin_off_res + sizeof(ExtRes) * c->xres.size() : c->xin_off_rec;
   // no event markers inside the chain (each one holds the next dispatch for microseconds): the pass is timed on the
   // host, from the input copy's enqueue to the end of the stream synchronisation (GS_EXT_EVENTS=1: per-kernel events)
-  static const bool ext_ev = getenv("GS_EXT_EVENTS") && getenv("GS_EXT_EVENTS")[0] == '1';
+  static const bool ext_ev = env_on("GS_EXT_EVENTS");
   const auto ext_t0 = std::chrono::steady_clock::now();
   HIP_TRY(c, hipMemcpyAsync(c->d_xin, c->h_xin, in_bytes, hipMemcpyHostToDevice, c->st));
   if (ext_ev) HIP_TRY(c, hipEventRecord(c->ev[0], c->st));
@@ -2209,34 +2176,18 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   // otherwise fills every CU while patch / cand wait for slots
   int prio_lo = 0, prio_hi = 0;
   if ((e = hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi)) != hipSuccess) return bail("hipDeviceGetStreamPriorityRange", e);
-  static const bool same_prio = getenv("GS_STREAM_PRIO") && getenv("GS_STREAM_PRIO")[0] == '0';
-  if (same_prio) prio_hi = prio_lo;
   // (Round 3 tried a CU partition here: the commit chain on CU-masked streams, the eval pass on the other CUs, with the
   // host applying a batch's placements one batch late. CU-masked streams are blocking streams — they synchronise with
   // the null stream, which hipMemset / hipMemcpy / hipFree use — and a one-pod-batch test hung in gs_destroy's hipFree
-  // with it; the commit measured no faster on a CU of its own (GS_COMMIT_EXCL). Removed)
+  // with it; the commit measured no faster on a CU of its own. Removed)
   if ((e = hipStreamCreateWithPriority(&c->st, hipStreamNonBlocking, prio_hi)) != hipSuccess) return bail("hipStreamCreate", e);
   if ((e = hipStreamCreateWithPriority(&c->st2, hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
   if ((e = hipStreamCreateWithPriority(&c->st_ev, hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
   if ((e = hipStreamCreateWithFlags(&c->st_rb, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
   if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
   if ((e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-  // GS_EV_FENCE (experiments): the device-side timing events 0, 1, 4 (and with "dev2" the eval-done events the commit
-  // stream waits on) recorded with a device-scope release ("dev") or no system-scope fence ("none") instead of the
-  // default system-scope release (an L2 write-back between the commit and the next kernel on its stream)
-  static const char* evf = getenv("GS_EV_FENCE");
-  const unsigned ev_fence = !evf ? 0u : !strncmp(evf, "dev", 3) ? (unsigned)hipEventReleaseToDevice
-                          : !strcmp(evf, "none") ? (unsigned)hipEventDisableSystemFence : 0u;
-  const bool evdone_fence = evf && !strcmp(evf, "dev2");
   for (int i = 0; i < 6; ++i)
-    if ((e = hipEventCreateWithFlags(&c->ev[i], (i == 0 || i == 1 || i == 4) ? ev_fence : 0u)) != hipSuccess)
-      return bail("hipEventCreate", e);
-  // GS_EV4_NT=1 (experiments): the commit-end event without timing (the levels interval then reads 0)
-  static const bool ev4_nt = getenv("GS_EV4_NT") && getenv("GS_EV4_NT")[0] == '1';
-  if (ev4_nt) {
-    (void)hipEventDestroy(c->ev[4]);
-    if ((e = hipEventCreateWithFlags(&c->ev[4], hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-  }
+    if ((e = hipEventCreate(&c->ev[i])) != hipSuccess) return bail("hipEventCreate", e);
   size_t np = c->npad;
   if ((e = hipMalloc(&c->d_i64, np * NUM_I64_COLS * 8)) != hipSuccess) return bail("hipMalloc mirror", e);
   if ((e = hipMalloc(&c->d_i32, np * NUM_I32_COLS * 4)) != hipSuccess) return bail("hipMalloc mirror", e);
@@ -2276,9 +2227,7 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   {
     for (auto& sl : c->slot) {
       if ((e = hipEventCreateWithFlags(&sl.ev_go, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-      if ((e = hipEventCreateWithFlags(&sl.ev_evdone, hipEventDisableTiming |
-                                                         (evdone_fence ? (unsigned)hipEventReleaseToDevice : 0u))) != hipSuccess)
-        return bail("hipEventCreate", e);
+      if ((e = hipEventCreateWithFlags(&sl.ev_evdone, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     }
     gs_ctx::Slot& s0 = c->slot[0];
     s0.d_S = c->d_S; s0.d_aff = c->d_aff;
@@ -2300,10 +2249,8 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
       return bail("hipHostMalloc", e);
     s1.h_out = reinterpret_cast<PlacementDev*>(s1.h_committed + COMMITTED_BYTES / 4);
     for (int i = 0; i < 6; ++i)
-      if ((e = hipEventCreateWithFlags(&s1.ev[i], i == 4 && ev4_nt ? hipEventDisableTiming
-                                                   : (i == 0 || i == 1 || i == 4) ? ev_fence : 0u)) != hipSuccess)
-        return bail("hipEventCreate", e);
-    c->cand_overlap = !(getenv("GS_CAND_OVERLAP") && getenv("GS_CAND_OVERLAP")[0] == '0');
+      if ((e = hipEventCreate(&s1.ev[i])) != hipSuccess) return bail("hipEventCreate", e);
+    c->cand_overlap = !env_off("GS_CAND_OVERLAP");
     if (c->cand_overlap)
       for (auto& sl : c->slot) {
         if ((e = hipMalloc(&sl.d_lst, xb)) != hipSuccess) return bail("hipMalloc", e);
@@ -2313,8 +2260,8 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
     c->d_hist = s0.d_hist;
   }
   if ((e = hipMalloc(&c->d_cscratch, cand_split_scratch_bytes())) != hipSuccess) return bail("hipMalloc", e);
-  c->host_timing = getenv("GS_HOST_TIMING") && getenv("GS_HOST_TIMING")[0] == '1';
-  if (getenv("GS_COMMIT_STAMPS") && getenv("GS_COMMIT_STAMPS")[0] == '1') {
+  c->host_timing = env_on("GS_HOST_TIMING");
+  if (env_on("GS_COMMIT_STAMPS")) {
     // 8 waves x 64 entries (commit_spec_kernel: one region per wave; the other commit kernels: region 0), then the
     // cand kernel's 8 at entry 512
     if ((e = hipMalloc(&c->d_stamps, 8 * 524)) != hipSuccess) return bail("hipMalloc", e);
@@ -2324,10 +2271,7 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   if ((e = hipDeviceSynchronize()) != hipSuccess) return bail("hipDeviceSynchronize", e);
   // 96 B (LoadAware + Fit row), + 192 B NodeNUMAResource columns when enabled
   c->stats.node_row_bytes = 3 * 8 + 4 + 2 * 8 + 2 * 8 + 2 * 8 + 2 * 8 + 4 + (c->numa_on ? 18 * 8 + 12 * 4 : 0);
-  if (const char* wd = getenv("GS_WATCHDOG_S")) {
-    const double lim = atof(wd);
-    if (lim > 0) c->watchdog = std::thread(watchdog_loop, c, lim);
-  }
+  if (const double lim = env_num("GS_WATCHDOG_S", 0.0); lim > 0) c->watchdog = std::thread(watchdog_loop, c, lim);
   *out = c;
   return GS_OK;
 }
@@ -2732,12 +2676,10 @@ int stage_batch(gs_ctx* c, const gs_pod* pods, const uint64_t* seq, uint32_t i, 
     HIP_TRY(c, hipEventRecord(sl.ev_go, c->st));
     HIP_TRY(c, hipStreamWaitEvent(c->st_ev, sl.ev_go, 0));
   }
-  // one copy: the B pod vectors' block (b of them staged) and the b sequence numbers after it (GS_MERGE_UP=0,
-  // experiments: two copies)
-  static const bool merge_up = !(getenv("GS_MERGE_UP") && getenv("GS_MERGE_UP")[0] == '0');
+  // one copy: the B pod vectors' block (b of them staged) and the b sequence numbers after it
   hipStream_t up = direct_batch(c, b, speculative) ? c->st : c->st_ev;
   // (the merged copy spans all B pod vectors, d_seq following the block: a short batch copies its b vectors and seq)
-  if (merge_up && 4 * b >= c->B) {
+  if (4 * b >= c->B) {
     HIP_TRY(c, hipMemcpyAsync(c->d_pods, c->h_pods, sizeof(PodVec) * c->B + 8 * b, hipMemcpyHostToDevice, up));
   } else {
     HIP_TRY(c, hipMemcpyAsync(c->d_pods, c->h_pods, sizeof(PodVec) * b, hipMemcpyHostToDevice, up));
@@ -2791,8 +2733,7 @@ int agree_next_run(gs_ctx* c, bool* use) {
 // (rc 0), or it failed; on an error the current run gets the error and a run already taken from next_run GS_ESTATE.
 template <class Next, class Done>
 int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
-  static const bool no_spec = getenv("GS_NO_PIPELINE") && getenv("GS_NO_PIPELINE")[0] == '1';
-  const bool can_spec = !no_spec;
+  static const bool can_spec = !env_on("GS_NO_PIPELINE");
   PodRun nxt{};
   bool have_nxt = false;
   auto drain = [&]() {
@@ -2820,9 +2761,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
   // Deferred application: a batch that committed every pod with no host work and no special pod changes no row on
   // the host side (apply_placement / numa_reserve only mirror what the commit wrote to HBM), so its placements are
   // applied to the host state after the batch two ahead is launched — the eval pass then starts right as the previous
-  // commit ends instead of after the host's ~0.2 ms of bookkeeping, and runs beside the next commit (GS_DEFER_APPLY=0:
-  // apply first).
-  static const bool defer_ok = !(getenv("GS_DEFER_APPLY") && getenv("GS_DEFER_APPLY")[0] == '0');
+  // commit ends instead of after the host's ~0.2 ms of bookkeeping, and runs beside the next commit.
   struct Pend {
     const gs_pod* pods = nullptr;
     gs_placement* out = nullptr;
@@ -2925,7 +2864,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       }
       if (rc) { if (spec) drain(); return rc; }
       const bool host_work = c->h_committed[1] != 1;   // the device-side continuation flag the speculative pass read
-      if (defer_ok && spec && !host_work && !cur_special && committed == cur_b) {
+      if (spec && !host_work && !cur_special && committed == cur_b) {
         // no host row changes: keep the results (this slot's buffers are reused by the batch two ahead) and apply them
         // after that batch is launched
         pend_out.assign(c->h_out, c->h_out + committed);

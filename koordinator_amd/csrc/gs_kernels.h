@@ -108,7 +108,6 @@ struct CommitArgs {
   uint32_t window_k;
   uint32_t start;
   uint32_t nnodes;
-  uint32_t dbg;              // diagnostics: bit 0 = the speculative commit waits for every pending row (no speculation)
   int32_t* tb;               // [npods x TB_N] selectHost tie-break records of each pod (speculative commit scratch)
   const int32_t* xerr;       // several shards: nonzero = the all-gathered blocks' exchange tags disagree (merge_levels)
 };
@@ -154,7 +153,7 @@ struct CandPatch {
   uint32_t* hist;
 };
 // split_scratch (cand_split_scratch_bytes()): a short batch (<= CS_MAXB pods, no patch) spreads each row over up to
-// CS_GMAX slices (cs_hist / cs_pick / cs_list kernels, GS_CAND_SPLIT=0 disables); nullptr: cand_kernel always
+// CS_GMAX slices (cs_hist / cs_pick / cs_list kernels); nullptr: cand_kernel always
 constexpr int CS_GMAX = 64, CS_MAXB = 32;
 size_t cand_split_scratch_bytes();
 hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int npods, int max_score, int lcap,
@@ -200,12 +199,6 @@ hipError_t launch_unpack_scores(const uint8_t* xin, size_t xblock, int nranks, i
 size_t commit_smem_bytes(int B);
 bool commit_spec_selected(uint32_t window_k);   // the speculative commit kernel runs (else pipelined / lockstep)
 hipError_t launch_commit(const CommitArgs& a, hipStream_t st);        // window_k > 0: lockstep kernel
-// GS_COMMIT_EXCL=1: the commit's workgroup holds a CU of its own: it declares the whole LDS of the CU and the eval
-// pass that overlaps it declares eval_lds_bytes(), so the dispatcher never places eval waves beside it. Measured
-// neutral on C3 (commit 0.705 vs 0.708 ms per batch): off by default.
-constexpr uint32_t LDS_PER_CU = 160u * 1024u;
-bool commit_cu_exclusive();
-size_t eval_lds_bytes();
 hipError_t launch_commit_spec(const CommitArgs& a, hipStream_t st);   // speculative pipeline (gs_commit_spec.hip)
 hipError_t set_commit_spec_attributes();
 hipError_t launch_row_stats(const int16_t* S, uint32_t len, RowStat* out, hipStream_t st);

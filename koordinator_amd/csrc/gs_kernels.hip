@@ -16,13 +16,11 @@
 // int64 with an exact reciprocal-estimate-plus-correction division (quotients lie in [0,100]).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <cstdio>
 #include <vector>
 
 #include "gs_eval_dev.h"
-#include "gs_pair_wave.h"
 
 namespace gs {
 
@@ -83,19 +81,16 @@ __global__ void __launch_bounds__(256) eval_kernel(MirrorView m, const PodVec* _
 }
 
 // The NUMA-topology-policy nodes of the shard (host-maintained ascending index list): hints over zone subsets,
-// the topology-manager merge, Allocate by hint. A thread keeps one node row in registers and evaluates PPT
-// consecutive pods of the batch: the row (gathered through the index list, ~30% of the shard's lines) is read
-// once per PPT pods instead of once per pair, while a full batch still puts ~nidx*B/PPT threads in flight.
+// the topology-manager merge, Allocate by hint. One (row, pod) pair per thread (the row gathered through the index
+// list): the form short batches run, where it keeps the grid wide; full batches run the tiled form below.
 // sv.i64 != nullptr: the rows come from the batch's slab (gather_numa_kernel: entry t = node idx[t], dense columns).
-template <int PPT>
 __global__ void __launch_bounds__(256) eval_numa_kernel(MirrorView m, MirrorView sv, const PodVec* __restrict__ pods,
                                                         int npods, Profile pf, const uint32_t* __restrict__ idx,
                                                         uint32_t nidx, uint32_t n0, int16_t* __restrict__ S, uint32_t ld,
                                                         int prod_cols, uint8_t* __restrict__ aff) {
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  const int k0 = blockIdx.y * PPT;
-  if (t >= nidx || k0 >= npods) return;
-  const int k1 = min(npods, k0 + PPT);
+  const int k = blockIdx.y;
+  if (t >= nidx || k >= npods) return;
   const uint32_t node = idx[t];
   Row row;
   if (sv.i64) {
@@ -104,43 +99,34 @@ __global__ void __launch_bounds__(256) eval_numa_kernel(MirrorView m, MirrorView
   } else {
     load_row(m, node, prod_cols, true, row);
   }
-  for (int k = k0; k < k1; ++k) {
-    PairOut o = eval_pair<false, false, true>(row, pods[k], pf, m);
-    S[(size_t)k * ld + (node - n0)] = (int16_t)total_score(o, pf);
-    aff[(size_t)k * ld + (node - n0)] = (uint8_t)(o.code ? 0u : o.aff);   // read by the commit's Reserve
-  }
+  PairOut o = eval_pair<false, false, true>(row, pods[k], pf, m);
+  S[(size_t)k * ld + (node - n0)] = (int16_t)total_score(o, pf);
+  aff[(size_t)k * ld + (node - n0)] = (uint8_t)(o.code ? 0u : o.aff);   // read by the commit's Reserve
 }
 
-// Tiled form (the default for full batches, PPT 8): a workgroup is a tile of 64 policy rows x NUMA_TWAVES * PPT pods; lane
-// = row, wave w = pods [w * PPT, (w + 1) * PPT) of the workgroup's pod range. The waves of a workgroup read the same
+// Tiled form (full batches): a workgroup is a tile of 64 policy rows x NUMA_TWAVES * NUMA_TILE_PPT pods; lane = row,
+// wave w = pods [w * NUMA_TILE_PPT, (w + 1) * NUMA_TILE_PPT) of the workgroup's pod range. The waves of a workgroup read the same
 // rows (one fetch from HBM, three cache hits), and the workgroups of one tile are numbered so they land on one XCD
 // (blocks go round-robin over the 8 XCDs: id % 8 = tile % 8) and are dispatched together (ids of 8 consecutive tiles x
 // every pod range form one run of ids), so each tile leaves HBM about once per pass instead of once per pod group
 // (round 4: ~26 reads of the slab per pass, 140 MB for a 4.6 MB slab at C3). ntiles8: tiles rounded up to 8.
 constexpr int NUMA_TWAVES = 4;
-template <int PPT>
+constexpr int NUMA_TILE_PPT = 8;   // pods per thread
 __global__ void __launch_bounds__(64 * NUMA_TWAVES) eval_numa_tile_kernel(MirrorView m, MirrorView sv,
                                                                           const PodVec* __restrict__ pods, int npods,
                                                                           Profile pf, const uint32_t* __restrict__ idx,
                                                                           uint32_t nidx, uint32_t n0, int16_t* __restrict__ S,
                                                                           uint32_t ld, int prod_cols,
-                                                                          uint8_t* __restrict__ aff, uint32_t npr,
-                                                                          int xcd_map) {
+                                                                          uint8_t* __restrict__ aff, uint32_t npr) {
   const uint32_t id = blockIdx.x;
-  uint32_t pr, tile;
-  if (xcd_map) {
-    const uint32_t grp = id / (8u * npr), rem = id % (8u * npr);
-    pr = rem / 8u;
-    tile = grp * 8u + rem % 8u;
-  } else {
-    pr = id % npr;
-    tile = id / npr;
-  }
+  const uint32_t grp = id / (8u * npr), rem = id % (8u * npr);
+  const uint32_t pr = rem / 8u;
+  const uint32_t tile = grp * 8u + rem % 8u;
   const uint32_t t = tile * 64u + (threadIdx.x & 63u);
   const int w = threadIdx.x >> 6;
-  const int k0 = (int)pr * (NUMA_TWAVES * PPT) + w * PPT;
+  const int k0 = (int)pr * (NUMA_TWAVES * NUMA_TILE_PPT) + w * NUMA_TILE_PPT;
   if (t >= nidx || k0 >= npods) return;
-  const int k1 = min(npods, k0 + PPT);
+  const int k1 = min(npods, k0 + NUMA_TILE_PPT);
   const uint32_t node = idx[t];
   Row row;
   if (sv.i64) {
@@ -212,41 +198,6 @@ __global__ void __launch_bounds__(128) patch_kernel(MirrorView m, const PodVec* 
   }
 }
 
-// The same patch with one wave per (row, pod) pair, lane-parallel (pair_score_wave): the kernel's time is the
-// slowest pair's, and a pair evaluated by one lane runs the rare long paths (the full topology-manager merge) as one
-// scalar chain, while a wave spreads them over its lanes. Block = one landed row x PW_PODS pods. The Filter-time
-// affinity of a patched NUMA-policy row is left to the Reserve (AFF_RECOMPUTE: numa_eval recomputes it there).
-constexpr int PW_PODS = 16;
-__global__ void __launch_bounds__(64 * PW_PODS) patch_wave_kernel(MirrorView m, const PodVec* __restrict__ pods,
-                                                                  int npods, Profile pf, uint32_t n0, uint32_t n1,
-                                                                  int16_t* __restrict__ S, uint32_t ld, int prod_cols,
-                                                                  uint8_t* __restrict__ aff,
-                                                                  const PlacementDev* __restrict__ prev_out,
-                                                                  const int32_t* __restrict__ prev_committed) {
-  const int k = blockIdx.x;
-  if (k >= prev_committed[0]) return;   // pods the previous batch placed (a voided pass: -1)
-  const int32_t node = prev_out[k].node;
-  if (node < 0 || (uint32_t)node < n0 || (uint32_t)node >= n1) return;
-  const bool numa = (pf.enabled & 0x30u) != 0;
-  __shared__ Row s_row;
-  __shared__ PodVec s_pod[PW_PODS];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = blockIdx.y * PW_PODS + w;
-  if (threadIdx.x == 0) {
-    load_row(m, (uint32_t)node, prod_cols, numa, s_row);
-    for (int sl = 3; sl < 7; ++sl) s_row.free[sl] = m.c64(C_FREE_CPU + sl)[node];
-  }
-  if (q < npods && lane < (int)(sizeof(PodVec) / 8))
-    reinterpret_cast<uint64_t*>(&s_pod[w])[lane] = reinterpret_cast<const uint64_t*>(&pods[q])[lane];
-  __syncthreads();
-  if (q >= npods) return;
-  const int32_t sc = pair_score_wave(s_row, s_pod[w], pf, m);
-  if (lane == 0) {
-    S[(size_t)q * ld + ((uint32_t)node - n0)] = (int16_t)sc;
-    if (numa && ((s_row.nr.nflags >> NF_POLICY_SHIFT) & 3u)) aff[(size_t)q * ld + ((uint32_t)node - n0)] = AFF_RECOMPUTE;
-  }
-}
-
 // Diagnostic variant (gs_evaluate): every plugin's verdict and score for every pair.
 __global__ void __launch_bounds__(256) eval_full_kernel(MirrorView m, const PodVec* __restrict__ pods, int npods,
                                                         Profile pf, uint32_t N, int16_t* scores, uint16_t* codes,
@@ -270,14 +221,15 @@ __global__ void __launch_bounds__(256) eval_full_kernel(MirrorView m, const PodV
 
 // ------------------------------------------------------------------------------------------------
 // Candidate levels: one workgroup (W waves) per pod row of the shard; wave w owns a contiguous W-th of the
-// row so that per-wave histograms give every wave its output offset within each level. W = 16 for profiles
-// with small score ranges (more bandwidth per row when batches are short), else 4.
-template <int W>
-__global__ void __launch_bounds__(64 * W) cand_kernel(int16_t* __restrict__ S, uint32_t ld, uint32_t len,
-                                                      uint32_t n0, int max_score, int lcap, uint32_t* __restrict__ lists,
-                                                      LevelHdr* __restrict__ hdrs, LevelExt* __restrict__ ext,
-                                                      uint64_t* stamps, CandPatch cp) {
-  constexpr int CAND_THREADS = 64 * W;
+// row so that per-wave histograms give every wave its output offset within each level. (A 16-wave form measured
+// slower on MI355X, its serial level scan walking 4x more segments: removed.)
+constexpr int CAND_WAVES = 4;
+__global__ void __launch_bounds__(64 * CAND_WAVES) cand_kernel(int16_t* __restrict__ S, uint32_t ld, uint32_t len,
+                                                               uint32_t n0, int max_score, int lcap,
+                                                               uint32_t* __restrict__ lists, LevelHdr* __restrict__ hdrs,
+                                                               LevelExt* __restrict__ ext, uint64_t* stamps,
+                                                               CandPatch cp) {
+  constexpr int W = CAND_WAVES, CAND_THREADS = 64 * W;
   // diagnostics (stamps != nullptr): wave 0's cycles per phase, summed over the pods
   uint64_t ct_last = stamps ? __builtin_amdgcn_s_memtime() : 0;
   auto CT = [&](int i) {
@@ -2015,13 +1967,6 @@ hipError_t launch_node_prep_idx(const MirrorView& m, const uint32_t* idx, uint32
   return hipGetLastError();
 }
 
-bool commit_cu_exclusive() {
-  static const bool on = getenv("GS_COMMIT_EXCL") && atoi(getenv("GS_COMMIT_EXCL")) != 0;
-  return on;
-}
-
-size_t eval_lds_bytes() { return commit_cu_exclusive() ? 256 : 0; }
-
 hipError_t launch_eval(const MirrorView& m, const PodVec* pods, int npods, const Profile& pf, uint32_t n0, uint32_t n1,
                        int16_t* S, uint32_t ld, int prod_cols, const uint32_t* numa_idx, uint32_t numa_n,
                        uint8_t* aff, hipStream_t st, hipStream_t st2, hipEvent_t fork, hipEvent_t join,
@@ -2030,7 +1975,6 @@ hipError_t launch_eval(const MirrorView& m, const PodVec* pods, int npods, const
   uint32_t gx = (len + 255) / 256;
   uint32_t gy = (npods + PODS_PER_BLOCK - 1) / PODS_PER_BLOCK;
   if (gx == 0 || gy == 0) return hipSuccess;
-  const size_t xl = eval_lds_bytes();
   if (pf.enabled & 0x30u) {
     // eval_kernel (nodes without a NUMA policy) and eval_numa_kernel write disjoint score entries: with a side
     // stream they run concurrently, eval_kernel's blocks filling the CUs eval_numa_kernel's low-occupancy waves
@@ -2041,54 +1985,30 @@ hipError_t launch_eval(const MirrorView& m, const PodVec* pods, int npods, const
       if ((e = hipEventRecord(fork, st)) != hipSuccess) return e;
       if ((e = hipStreamWaitEvent(st2, fork, 0)) != hipSuccess) return e;
     }
-    // short batches: one pair per thread keeps the grid wide
-    static const int ppt_env = getenv("GS_NUMA_PPT") ? atoi(getenv("GS_NUMA_PPT")) : NUMA_PPT;
-    const int ppt = npods >= 32 ? ppt_env : 1;
-    const dim3 g((numa_n + 255) / 256, (npods + ppt - 1) / ppt);
     // the slab pays once a row is read by several pod groups (full batches)
+    const bool full = npods >= 32;
     MirrorView sv{nullptr, nullptr, 0};
-    if (slab && slab->i64 && numa_n && npods >= 32) {
+    if (slab && slab->i64 && numa_n && full) {
       sv = *slab;
-      hipLaunchKernelGGL(gather_numa_kernel, dim3((numa_n + 255) / 256, SLAB64 + SLAB32), dim3(256), xl, st, m, sv,
+      hipLaunchKernelGGL(gather_numa_kernel, dim3((numa_n + 255) / 256, SLAB64 + SLAB32), dim3(256), 0, st, m, sv,
                          numa_idx, numa_n);
     }
-    // GS_NUMA_TILE=0 (experiments): the untiled grid
-    // (GS_NUMA_TILE=2: tiled without the XCD numbering)
-    static const int tile_mode = getenv("GS_NUMA_TILE") ? atoi(getenv("GS_NUMA_TILE")) : 1;
-    const bool tile = tile_mode != 0;
     if (numa_n == 0) {
-    } else if (tile && ppt == NUMA_PPT) {
-      // pods per thread of the tiled kernel: 8 (GS_NUMA_TILE_PPT: 2, 4, 8). Tiled, 8 pods per thread: 337 us per pass
-      // and 2.4 MB of reads; untiled (4): 241 us and 58.5 MB. The pass runs beside the previous batch's commit, which
-      // it slows less when tiled: 182.8-183.7k vs 180.0-180.5k pods/s in three alternations
-      static const int tppt = getenv("GS_NUMA_TILE_PPT") ? atoi(getenv("GS_NUMA_TILE_PPT")) : 8;
+    } else if (full) {
+      // Tiled, 8 pods per thread: 337 us per pass and 2.4 MB of reads; untiled (4): 241 us and 58.5 MB. The pass runs
+      // beside the previous batch's commit, which it slows less when tiled: 182.8-183.7k vs 180.0-180.5k pods/s in
+      // three alternations
       const uint32_t ntiles8 = ((numa_n + 63) / 64 + 7) / 8 * 8;
-      const uint32_t npr = (npods + NUMA_TWAVES * tppt - 1) / (NUMA_TWAVES * tppt);
-      const int xm = tile_mode == 1 ? 1 : 0;
-      if (tppt == 2)
-        hipLaunchKernelGGL(eval_numa_tile_kernel<2>, dim3(ntiles8 * npr), dim3(64 * NUMA_TWAVES), xl, st, m, sv, pods,
-                           npods, pf, numa_idx, numa_n, n0, S, ld, prod_cols, aff, npr, xm);
-      else if (tppt == 8)
-        hipLaunchKernelGGL(eval_numa_tile_kernel<8>, dim3(ntiles8 * npr), dim3(64 * NUMA_TWAVES), xl, st, m, sv, pods,
-                           npods, pf, numa_idx, numa_n, n0, S, ld, prod_cols, aff, npr, xm);
-      else
-        hipLaunchKernelGGL(eval_numa_tile_kernel<NUMA_PPT>, dim3(ntiles8 * npr), dim3(64 * NUMA_TWAVES), xl, st, m, sv,
-                           pods, npods, pf, numa_idx, numa_n, n0, S, ld, prod_cols, aff, npr, xm);
-    } else if (ppt == 2) {
-      hipLaunchKernelGGL(eval_numa_kernel<2>, g, dim3(256), xl, st, m, sv, pods, npods, pf, numa_idx, numa_n, n0, S, ld,
-                         prod_cols, aff);
-    } else if (ppt == 4) {
-      hipLaunchKernelGGL(eval_numa_kernel<4>, g, dim3(256), xl, st, m, sv, pods, npods, pf, numa_idx, numa_n, n0, S, ld,
-                         prod_cols, aff);
-    } else if (ppt == 8) {
-      hipLaunchKernelGGL(eval_numa_kernel<8>, g, dim3(256), xl, st, m, sv, pods, npods, pf, numa_idx, numa_n, n0, S, ld,
-                         prod_cols, aff);
+      const uint32_t npr = (npods + NUMA_TWAVES * NUMA_TILE_PPT - 1) / (NUMA_TWAVES * NUMA_TILE_PPT);
+      hipLaunchKernelGGL(eval_numa_tile_kernel, dim3(ntiles8 * npr), dim3(64 * NUMA_TWAVES), 0, st, m, sv, pods, npods,
+                         pf, numa_idx, numa_n, n0, S, ld, prod_cols, aff, npr);
     } else {
-      hipLaunchKernelGGL(eval_numa_kernel<1>, dim3((numa_n + 255) / 256, npods), dim3(256), xl, st, m, sv, pods, npods,
-                         pf, numa_idx, numa_n, n0, S, ld, prod_cols, aff);
+      // short batches: one pair per thread keeps the grid wide
+      hipLaunchKernelGGL(eval_numa_kernel, dim3((numa_n + 255) / 256, npods), dim3(256), 0, st, m, sv, pods, npods, pf,
+                         numa_idx, numa_n, n0, S, ld, prod_cols, aff);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(eval_kernel<true>, dim3(gx, gy), dim3(256), xl, side ? st2 : st, m, pods, npods, pf, n0, n1, S,
+    hipLaunchKernelGGL(eval_kernel<true>, dim3(gx, gy), dim3(256), 0, side ? st2 : st, m, pods, npods, pf, n0, n1, S,
                        ld, prod_cols);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (side) {
@@ -2096,7 +2016,7 @@ hipError_t launch_eval(const MirrorView& m, const PodVec* pods, int npods, const
       if ((e = hipStreamWaitEvent(st, join, 0)) != hipSuccess) return e;
     }
   } else {
-    hipLaunchKernelGGL(eval_kernel<false>, dim3(gx, gy), dim3(256), xl, st, m, pods, npods, pf, n0, n1, S, ld, prod_cols);
+    hipLaunchKernelGGL(eval_kernel<false>, dim3(gx, gy), dim3(256), 0, st, m, pods, npods, pf, n0, n1, S, ld, prod_cols);
   }
   return hipGetLastError();
 }
@@ -2105,14 +2025,9 @@ hipError_t launch_patch(const MirrorView& m, const PodVec* pods, int npods, cons
                         int16_t* S, uint32_t ld, int prod_cols, uint8_t* aff, const PlacementDev* prev_out,
                         const int32_t* prev_committed, int prev_npods, hipStream_t st) {
   if (prev_npods <= 0 || npods <= 0) return hipSuccess;
-  // one lane per pair (default: 63 us per C3 batch); GS_PATCH_WAVE=1: one wave per pair (measured 91 us)
-  static const bool wave = getenv("GS_PATCH_WAVE") && getenv("GS_PATCH_WAVE")[0] == '1';
-  if (!wave)
-    hipLaunchKernelGGL(patch_kernel, dim3(prev_npods), dim3(128), 0, st, m, pods, npods, pf, n0, n1, S, ld, prod_cols,
-                       aff, prev_out, prev_committed);
-  else
-    hipLaunchKernelGGL(patch_wave_kernel, dim3(prev_npods, (npods + PW_PODS - 1) / PW_PODS), dim3(64 * PW_PODS), 0, st,
-                       m, pods, npods, pf, n0, n1, S, ld, prod_cols, aff, prev_out, prev_committed);
+  // one lane per pair: 63 us per C3 batch (one wave per pair measured 91 us: removed)
+  hipLaunchKernelGGL(patch_kernel, dim3(prev_npods), dim3(128), 0, st, m, pods, npods, pf, n0, n1, S, ld, prod_cols, aff,
+                     prev_out, prev_committed);
   return hipGetLastError();
 }
 
@@ -2124,15 +2039,9 @@ hipError_t launch_eval_full(const MirrorView& m, const PodVec* pods, int npods, 
   return hipGetLastError();
 }
 
-static size_t cand_smem_bytes(int max_score, int waves) {
+static size_t cand_smem_bytes(int max_score) {
   size_t nb = (size_t)max_score + 1;
-  return nb * 4 * waves + nb * 4 + ((nb + 15) & ~(size_t)15);
-}
-// The 16-wave variant measured slower on MI355X (its serial level scan walks 4x more segments): kept for
-// experiments, not selected.
-static bool cand_wide(int max_score) {
-  static const int env = getenv("GS_CAND_WIDE") ? atoi(getenv("GS_CAND_WIDE")) : 0;
-  return env == 1 && cand_smem_bytes(max_score, 16) <= 48 * 1024;
+  return nb * 4 * CAND_WAVES + nb * 4 + ((nb + 15) & ~(size_t)15);
 }
 
 static uint64_t* g_cand_stamps = nullptr;
@@ -2159,9 +2068,8 @@ hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int n
   if (lcap < 1 || lcap > LCAP) return hipErrorInvalidValue;
   CandPatch cp{};
   if (patch) cp = *patch;
-  static const bool no_split = getenv("GS_CAND_SPLIT") && getenv("GS_CAND_SPLIT")[0] == '0';
   const uint32_t lenv = (len + 511) & ~511u;
-  if (split_scratch && !no_split && !cp.on && !cp.hist && cp.extra == 0 && !g_cand_stamps && npods >= 1 &&
+  if (split_scratch && !cp.on && !cp.hist && cp.extra == 0 && !g_cand_stamps && npods >= 1 &&
       npods <= CS_MAXB && max_score >= 0 && max_score <= MAX_SCORE_LIMIT && lenv >= 2 * 2048) {
     // slices of whole 2048-entry steps, at most CS_GMAX of them (rows are padded with -1 up to ld >= lenv)
     const uint32_t g0 = min((uint32_t)CS_GMAX, (lenv + 2047) / 2048);
@@ -2178,12 +2086,8 @@ hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int n
                        n0, nbins, slice, G, lcap, offs, hdrs, ext, lists);
     return hipGetLastError();
   }
-  if (cand_wide(max_score))
-    hipLaunchKernelGGL(cand_kernel<16>, dim3(npods), dim3(1024), cand_smem_bytes(max_score, 16), st, S, ld, len, n0,
-                       max_score, lcap, lists, hdrs, ext, g_cand_stamps, cp);
-  else
-    hipLaunchKernelGGL(cand_kernel<4>, dim3(npods), dim3(256), cand_smem_bytes(max_score, 4), st, S, ld, len, n0,
-                       max_score, lcap, lists, hdrs, ext, g_cand_stamps, cp);
+  hipLaunchKernelGGL(cand_kernel, dim3(npods), dim3(64 * CAND_WAVES), cand_smem_bytes(max_score), st, S, ld, len, n0,
+                     max_score, lcap, lists, hdrs, ext, g_cand_stamps, cp);
   return hipGetLastError();
 }
 
@@ -2238,11 +2142,8 @@ hipError_t set_kernel_attributes() {
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(commit_kernel<true>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit_smem_bytes(MAX_BATCH));
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(cand_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          48 * 1024);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(cand_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)cand_smem_bytes(MAX_SCORE_LIMIT, 4));
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(cand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)cand_smem_bytes(MAX_SCORE_LIMIT));
 }
 
 }  // namespace gs

@@ -792,7 +792,7 @@ extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t l
                "interleave %d, %s, %d cores, maxRefCount %d) host %llx %llx dev %llx %llx", hok, dok, needed, bind, ep,
                strategy, cpc, interleave, shape, ncores, mr, (unsigned long long)h.w[0], (unsigned long long)h.w[1],
                (unsigned long long)w[0], (unsigned long long)w[1]);
-      if (getenv("GSX_SELFTEST_DUMP")) {
+      if (env_str("GSX_SELFTEST_DUMP")) {
         fprintf(stderr, "cpu core node ref excl avail:\n");
         for (int c = 0; c < in.num_cpus; ++c)
           fprintf(stderr, "  %d %d %d %d %d %d\n", c, in.core_id[c], in.node_id[c], n.ref[c], n.excl[c], avail.has(c));

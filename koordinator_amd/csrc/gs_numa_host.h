@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <cstdlib>
 #include <map>
 #include <memory>
 #include <unordered_map>
@@ -14,6 +15,12 @@
 #include "gs_cpuset_dev.h"
 
 namespace gs {
+
+// Environment switches (the table in DESIGN.md lists every one): "1" turns on, "0" turns off, a number, a string
+inline const char* env_str(const char* name) { return getenv(name); }
+inline bool env_on(const char* name) { const char* v = env_str(name); return v && v[0] == '1'; }
+inline bool env_off(const char* name) { const char* v = env_str(name); return v && v[0] == '0'; }
+inline double env_num(const char* name, double dflt) { const char* v = env_str(name); return v ? atof(v) : dflt; }
 
 struct CpuMask {
   uint64_t w[GS_CPU_WORDS] = {0, 0, 0, 0};
