@@ -263,7 +263,8 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     resv[i] = 0;
   }
   for (int i = tid; i < SP_HASH; i += SP_THREADS) { hkey[i] = -1; hval[i] = -1; }
-  for (int i = tid; i < B; i += SP_THREADS) tiebreak_records(a.seed, a.seq[i], a.tb + (size_t)i * TB_N);
+  if (!a.tb_ready)   // (else cand_kernel wrote them beside the previous batch's commit)
+    for (int i = tid; i < B; i += SP_THREADS) tiebreak_records(a.seed, a.seq[i], a.tb + (size_t)i * TB_N);
   if (tid == 0) {
     s_decided = 0; s_stop = 0; s_parked = 0; s_finish = 0; s_cut_at = -1; s_err = 0; s_werr = 0;
     for (int k = 0; k < SP_NRES; ++k) { s_jq_head[k] = 0; s_jq_tail[k] = 0; }
@@ -1768,6 +1769,48 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       else if (j < 30) m.c64(C_CPU_UN0 + (j - 19))[node] = reinterpret_cast<const int64_t*>(&cst[sl])[j - 19];
       else m.c32(C_CPU_META)[node] = (int32_t)cst[sl].meta;
     }
+  // the rows the committed pods landed on, compact, for the next batch's fix-up (the landed slab, gs_kernels.h): whole
+  // Row images, NUMA-policy rows first. A slot counts when a committed pod's decision names it (a slot of a pod decided
+  // past a host cut holds its undone row: not landed).
+  if (a.landed) {
+    int32_t* lpos = jobs_left;   // (the pipeline is over: its per-pod counters are free) slot -> position, -1: not landed
+    int32_t* lh = reinterpret_cast<int32_t*>(a.landed);
+    for (int s = tid; s < SB; s += SP_THREADS) lpos[s] = -1;
+    __syncthreads();
+    for (int q = tid; q < committed; q += SP_THREADS)
+      if (!(dec[q].flags & SP_FITERR) && (uint32_t)dec[q].slot < (uint32_t)SB) lpos[dec[q].slot] = 0;
+    __syncthreads();
+    if (wv == 0) {
+      static_assert(SB == 128, "two slots per lane");
+      bool pol[2], non[2];
+      for (int h = 0; h < 2; ++h) {
+        const int s = h * 64 + lane;
+        const bool on = s < nd && has_row[s] && lpos[s] == 0;
+        pol[h] = on && numa_on && ((drows[s].nr.nflags >> NF_POLICY_SHIFT) & 3u);
+        non[h] = on && !pol[h];
+      }
+      const uint64_t p0 = __ballot(pol[0]), p1 = __ballot(pol[1]), n0 = __ballot(non[0]), n1 = __ballot(non[1]);
+      const int npol = __popcll(p0) + __popcll(p1);
+      WAVE_FENCE();
+      lpos[lane] = pol[0] ? __popcll(p0 & lt_mask) : non[0] ? npol + __popcll(n0 & lt_mask) : -1;
+      lpos[64 + lane] = pol[1] ? __popcll(p0) + __popcll(p1 & lt_mask)
+                               : non[1] ? npol + __popcll(n0) + __popcll(n1 & lt_mask) : -1;
+      if (lane == 0) {
+        lh[0] = npol + __popcll(n0) + __popcll(n1);
+        lh[1] = npol;
+      }
+    }
+    __syncthreads();
+    for (int s = tid; s < nd; s += SP_THREADS)
+      if (lpos[s] >= 0) lh[LANDED_NODES / 4 + lpos[s]] = (int32_t)drows[s].node;
+    constexpr int RW = (int)(sizeof(Row) / 8);
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(drows);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(a.landed + LANDED_ROWS);
+    for (int e = tid; e < nd * RW; e += SP_THREADS) {
+      const int s = e / RW;
+      if (lpos[s] >= 0) dst[lpos[s] * RW + (e - s * RW)] = src[e];
+    }
+  }
   for (int i = tid; i < committed; i += SP_THREADS) a.out[i].feasible = (uint32_t)final_F[i];
   if (ST && lane == 0)   // per wave: region wv of SP_STRIDE entries
     for (int i = 0; i < SP_NST; ++i)

@@ -163,7 +163,7 @@ struct gs_ctx {
   int lstride = LCAP;               // listed nodes per pod in the local / exchanged blocks (XCAP: several ranks, spec)
   PlacementDev* d_out = nullptr;
   int32_t* d_committed = nullptr;
-  int32_t* d_tb = nullptr;          // speculative commit: tie-break records of the batch's pods
+  int32_t* d_tb = nullptr;          // speculative commit: tie-break records of the batch's pods (the bound slot's)
   RowStat* d_rowstat = nullptr;
   int32_t* d_sel = nullptr;
   uint32_t* d_stage_idx = nullptr;
@@ -197,6 +197,8 @@ struct gs_ctx {
     bool untimed = false;           // the batch recorded no timing events (a short direct batch)
     uint8_t* d_lst = nullptr;       // overlapped cand (one shard): the slot's lists + headers, and its histograms
     uint32_t* d_hist = nullptr;
+    int32_t* d_tb = nullptr;        // the slot's tie-break records: cand_kernel writes the next batch's beside this commit
+    uint8_t* d_landed = nullptr;    // the landed slab the slot's commit leaves for the next batch's fix-up (cand_overlap)
   } slot[2];
   bool cand_overlap = false;        // GS_CAND_OVERLAP (default on): cand beside the previous commit, fix_levels after it
   uint8_t* d_lst = nullptr;         // the bound slot's (cand_overlap)
@@ -1246,6 +1248,7 @@ void bind_slot(gs_ctx* c, int s) {
   c->h_pods = x.h_pods; c->h_seq = x.h_seq; c->h_out = x.h_out; c->h_committed = x.h_committed;
   for (int i = 0; i < 6; ++i) c->ev[i] = x.ev[i];
   c->d_lst = x.d_lst; c->d_hist = x.d_hist;
+  c->d_tb = x.d_tb;
   c->cur_slot = s;
 }
 
@@ -1300,6 +1303,7 @@ CommitArgs commit_args(gs_ctx* c, int b) {
   a.start = c->next_start;
   a.nnodes = c->N;
   a.tb = c->d_tb;
+  a.landed = c->slot[c->cur_slot].d_landed;
   // (score rows: the batch slot's verdict of unpack_scores_kernel; levels: merge_levels_kernel's)
   a.xerr = c->sgather ? c->d_xerr + (XERR_BYTES / 4) * c->cur_slot : c->nranks > 1 ? c->d_xerr : nullptr;
   return a;
@@ -1382,14 +1386,20 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
     if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[1], se));
   }
   const bool fix = ovl && prev && prev_b > 0;
+  int32_t tb_ready = 0;
   if (ovl) {
     // levels on st_ev beside the previous batch's commit: the rows it lands on are stale here (listed with a margin of
     // prev_b nodes, histogram kept), fixed up on st below once it committed
     CandPatch cp{};
     cp.extra = fix ? prev_b : 0;
     cp.hist = fix ? c->d_hist : nullptr;
+    // the batch's tie-break records too (off the commit's prologue); a short batch split over cs_* kernels leaves them
+    // to the commit
+    cp.tb = c->d_tb;
+    cp.seq = c->d_seq;
+    cp.seed = c->cfg.seed;
     HIP_TRY(c, launch_cand(c->d_S, c->ld, len, c->n0, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, se, &cp,
-                           c->d_cscratch));
+                           c->d_cscratch, &tb_ready));
   }
   if (!direct) {
     HIP_TRY(c, hipEventRecord(sl.ev_evdone, c->st_ev));
@@ -1402,6 +1412,7 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
     CandPatch cp{c->mv, c->d_pods, c->pf, c->n0, c->n1, prod_cols, 0, c->d_aff, prev_out, prev};
     cp.extra = prev_b;
     cp.hist = c->d_hist;
+    cp.landed = c->slot[1 - c->cur_slot].d_landed;   // (a speculative pass: the previous batch is the other slot's)
     HIP_TRY(c, launch_fix_levels(c->d_S, c->ld, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, cp, c->st));
   }
   // the rows the previous batch landed on, re-evaluated on their committed state: inside cand_kernel (block k patches
@@ -1427,6 +1438,7 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
   }
   CommitArgs a = commit_args(c, b);
   a.prev = prev;
+  a.tb_ready = tb_ready;
   ++c->xbatch;
   HIP_TRY(c, launch_commit(a, c->st));
   if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[4], c->st));
@@ -2208,7 +2220,7 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   c->xchg_bytes = xb;
   if ((e = hipMalloc(&c->d_committed, COMMITTED_BYTES + sizeof(PlacementDev) * c->B)) != hipSuccess) return bail("hipMalloc", e);
   c->d_out = reinterpret_cast<PlacementDev*>(c->d_committed + COMMITTED_BYTES / 4);
-  if ((e = hipMalloc(&c->d_tb, sizeof(int32_t) * TB_N * c->B)) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = hipMalloc(&c->d_tb, sizeof(int32_t) * TB_N * c->B * 2)) != hipSuccess) return bail("hipMalloc", e);   // both slots'
   if ((e = hipMalloc(&c->d_rowstat, sizeof(RowStat) * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
   if ((e = hipMalloc(&c->d_sel, 4 * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
   c->stage_cap = std::min<uint32_t>(c->N, 65536);
@@ -2235,6 +2247,8 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
     s0.h_pods = c->h_pods; s0.h_seq = c->h_seq; s0.h_out = c->h_out; s0.h_committed = c->h_committed;
     for (int i = 0; i < 6; ++i) s0.ev[i] = c->ev[i];
     gs_ctx::Slot& s1 = c->slot[1];
+    s0.d_tb = c->d_tb;
+    s1.d_tb = c->d_tb + (size_t)TB_N * c->B;
     if ((e = hipMalloc(&s1.d_S, (size_t)c->B * c->ld * 2)) != hipSuccess) return bail("hipMalloc S", e);
     if ((e = hipMalloc(&s1.d_aff, (size_t)c->B * c->ld)) != hipSuccess) return bail("hipMalloc aff", e);
     (void)hipMemset(s1.d_S, 0xff, (size_t)c->B * c->ld * 2);
@@ -2255,6 +2269,8 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
       for (auto& sl : c->slot) {
         if ((e = hipMalloc(&sl.d_lst, xb)) != hipSuccess) return bail("hipMalloc", e);
         if ((e = hipMalloc(&sl.d_hist, (size_t)4 * c->B * (MAX_SCORE_LIMIT + 1))) != hipSuccess) return bail("hipMalloc", e);
+        if ((e = hipMalloc(&sl.d_landed, landed_slab_bytes())) != hipSuccess) return bail("hipMalloc", e);
+        (void)hipMemset(sl.d_landed, 0, landed_slab_bytes());
       }
     c->d_lst = s0.d_lst;
     c->d_hist = s0.d_hist;
@@ -2428,8 +2444,10 @@ int gs_destroy(gs_ctx* c) {
       for (auto& sl : c->slot) {
       if (sl.d_lst) (void)hipFree(sl.d_lst);
       if (sl.d_hist) (void)hipFree(sl.d_hist);
+      if (sl.d_landed) (void)hipFree(sl.d_landed);
       sl.d_lst = nullptr;
       sl.d_hist = nullptr;
+      sl.d_landed = nullptr;
     }
     c->d_lst = nullptr;
     c->d_hist = nullptr;

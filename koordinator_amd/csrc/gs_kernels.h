@@ -108,9 +108,18 @@ struct CommitArgs {
   uint32_t window_k;
   uint32_t start;
   uint32_t nnodes;
-  int32_t* tb;               // [npods x TB_N] selectHost tie-break records of each pod (speculative commit scratch)
+  int32_t* tb;               // [npods x TB_N] selectHost tie-break records of each pod (speculative commit)
+  int32_t tb_ready;          // cand_kernel wrote tb beside the previous commit (0: the commit's prologue computes it)
+  uint8_t* landed;           // the batch's landed slab out (speculative commit; nullptr: none), see LANDED_* below
   const int32_t* xerr;       // several shards: nonzero = the all-gathered blocks' exchange tags disagree (merge_levels)
 };
+// The landed slab: the rows a batch's committed pods landed on, as the speculative commit kernel leaves them (the
+// state its write-back gives the mirror), distinct nodes, rows with a NUMA topology policy first: int32 count, int32
+// count of policy rows, then at LANDED_NODES one int32 node per row, then at LANDED_ROWS the Row images (eval_pair's
+// LDS_SCALARS form: free[3..6] filled). The next batch's fix-up reads it instead of gathering the rows from the
+// mirror's columns. A voided pass writes nothing; after an expired wait the count is 0.
+constexpr size_t LANDED_NODES = 16, LANDED_ROWS = LANDED_NODES + 4 * MAX_BATCH;
+size_t landed_slab_bytes();
 // tiebreak_position(seed, seq, T) as a lookup: entries 0..TB_N-2 are the positions the reservoir walk visits
 // (ascending, independent of T; INT32_MAX past the walk's end), entry TB_N-1 the largest T the entries decide
 constexpr int TB_N = 32;
@@ -151,17 +160,26 @@ struct CandPatch {
   // (the previous batch's landed rows may leave the levels), hist = [pod][max_score + 1] the row's score histogram out
   int extra;
   uint32_t* hist;
+  // selectHost tie-break records of pod k into tb[k x TB_N] (tiebreak_records: a serial walk that needs only the
+  // seed and the pod's seq, taken off the commit kernel's prologue); tb = nullptr: not written
+  int32_t* tb;
+  const uint64_t* seq;
+  uint64_t seed;
+  // launch_fix_levels: the previous batch's landed slab
+  const uint8_t* landed;
 };
 // split_scratch (cand_split_scratch_bytes()): a short batch (<= CS_MAXB pods, no patch) spreads each row over up to
-// CS_GMAX slices (cs_hist / cs_pick / cs_list kernels); nullptr: cand_kernel always
+// CS_GMAX slices (cs_hist / cs_pick / cs_list kernels); nullptr: cand_kernel always. tb_written: 1 when patch->tb was
+// written (cand_kernel ran with it), else 0 (the split kernels do not write it)
 constexpr int CS_GMAX = 64, CS_MAXB = 32;
 size_t cand_split_scratch_bytes();
 hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int npods, int max_score, int lcap,
                        uint32_t* lists, LevelHdr* hdrs, LevelExt* ext, hipStream_t st, const CandPatch* patch = nullptr,
-                       uint32_t* split_scratch = nullptr);
-// The previous batch's landed rows folded into stale levels (cand_kernel with cp.extra / cp.hist, before that batch's
-// commit ended): the rows re-evaluated (S, aff patched as by cand_kernel's patch), the histogram updated, the levels
-// re-picked and each listed level rewritten as its stale nodes minus the landed rows plus the landed rows now at it
+                       uint32_t* split_scratch = nullptr, int32_t* tb_written = nullptr);
+// The previous batch's landed rows (cp.landed, the slab its commit left) folded into stale levels (cand_kernel with
+// cp.extra / cp.hist, before that batch's commit ended): the rows re-evaluated (S, aff patched as by cand_kernel's
+// patch), the histogram updated, the levels re-picked and each listed level rewritten as its stale nodes minus the
+// landed rows plus the landed rows now at it
 hipError_t launch_fix_levels(int16_t* S, uint32_t ld, int npods, int max_score, int lcap, uint32_t* lists,
                              LevelHdr* hdrs, LevelExt* ext, const CandPatch& cp, hipStream_t st);
 // Every all-gathered block ends with the sender's exchange tag: which exchange of the context's sequence it is (a

@@ -365,6 +365,9 @@ __global__ void __launch_bounds__(64 * CAND_WAVES) cand_kernel(int16_t* __restri
       s_nlev = nlev;
       s_next = next;
     }
+  } else if (t == 64 && cp.tb) {
+    // pod k's tie-break records, while this wave would wait for wave 0's level pick
+    tiebreak_records(cp.seed, cp.seq[k], cp.tb + (size_t)k * TB_N);
   }
   __syncthreads();
   CT(2);
@@ -682,18 +685,21 @@ __global__ void __launch_bounds__(FIX_THREADS) fix_levels_kernel(int16_t* __rest
   __shared__ int32_t s_wd[2];
   int8_t* lev_of = reinterpret_cast<int8_t*>(olist + lcap);   // [nbins] bin -> new level (-1: not listed)
   const int k = blockIdx.x, t = threadIdx.x, lane = t & 63;
-  // the landed node of entry t (cp.extra = the previous batch's size bounds its placements) loads beside the count
-  const int32_t node_t = t < cp.extra ? cp.prev_out[t].node : -1;
-  const int npr = min(cp.prev_committed[0], MAX_BATCH);   // -1: a voided pass (its lists are never used)
-  if (npr <= 0) return;
+  if (cp.prev_committed[0] <= 0) return;   // -1: a voided pass (its lists are never used)
+  // The landed rows come from the previous batch's slab (whole Row images the commit left, NUMA-policy rows first), not
+  // from the mirror's columns. Wave 0 takes the slab's front and wave 1 its back, split at the first row without a
+  // policy where both halves fit, so that a wave's lanes run the same evaluation path (a policy row's is the long one).
+  const int32_t* lh = reinterpret_cast<const int32_t*>(cp.landed);
+  const int nl = min(max(lh[0], 0), MAX_BATCH), npol = min(max(lh[1], 0), nl);
+  const int split = min(max(npol, nl - 64), 64);
+  const int slot_t = t < 64 ? (t < split ? t : -1) : (t < 128 && split + (t - 64) < nl ? split + (t - 64) : -1);
+  const int32_t node_t = slot_t >= 0 ? lh[LANDED_NODES / 4 + slot_t] : -1;
   __shared__ unsigned int s_ev_max[2];   // diagnostics: the block's slowest lane (row loads, row loads + evaluation)
   if (stamps && t < 2) s_ev_max[t] = 0;
   if (stamps) __syncthreads();
-  // phase 1 (no barrier): the evaluation of the landed rows is the long chain (row loads ~15k cycles, then one pair
-  // evaluation, ~26k for the slowest lane of a wave whose rows differ), so waves 0-1 do only that: thread j < npr
-  // evaluates landed entry j (duplicates too: a node several pods landed on gives the same result each time; its stale
-  // score is read here, before any entry's write below). Beside it wave 3 reads the stale levels and stages the stale
-  // lists in LDS, and wave 2 the histogram (their HBM round trips overlap the evaluation).
+  // phase 1 (no barrier): the evaluation of the landed rows is the long chain (the row's image, then one pair
+  // evaluation), so waves 0-1 do only that. Beside it wave 3 reads the stale levels and stages the stale lists in LDS,
+  // and wave 2 the histogram (their HBM round trips overlap the evaluation).
   static_assert(FIX_THREADS == 256 && MAX_BATCH <= 128, "fix_levels_kernel: waves 0-1 evaluate, 2-3 load");
   if (t >= FIX_THREADS - 64) {   // the stale levels: one lane per level (independent loads), offsets by a wave scan
     const LevelHdr& h = hdrs[k];
@@ -741,7 +747,7 @@ __global__ void __launch_bounds__(FIX_THREADS) fix_levels_kernel(int16_t* __rest
   size_t at = 0;
   int so = -1, sn = -1, aff_v = -1;
   bool valid = false;
-  if (t < npr) {
+  if (t < 128) {
     const int32_t node = node_t;
     valid = node >= 0 && (uint32_t)node >= cp.n0 && (uint32_t)node < cp.n1;
     p_raw[t] = valid ? (uint32_t)node : 0xffffffffu;
@@ -751,13 +757,12 @@ __global__ void __launch_bounds__(FIX_THREADS) fix_levels_kernel(int16_t* __rest
         atomicAdd(reinterpret_cast<unsigned long long*>(&stamps[10]), (unsigned long long)(e0 - ct_last));
       at = (size_t)k * ld + ((uint32_t)node - cp.n0);
       so = S[at];
-      Row r;
-      load_row(cp.m, (uint32_t)node, cp.prod_cols, numa, r);
+      const Row r = reinterpret_cast<const Row*>(cp.landed + LANDED_ROWS)[slot_t];
       if (stamps) {
         __builtin_amdgcn_s_waitcnt(0);
         atomicMax(&s_ev_max[0], (unsigned int)(__builtin_amdgcn_s_memtime() - e0));
       }
-      const PairOut o = eval_pair<false, false, true>(r, cp.pods[k], cp.pf, cp.m);
+      const PairOut o = eval_pair<false, true, true>(r, cp.pods[k], cp.pf, cp.m);   // (free[3..6] are in the image)
       sn = total_score(o, cp.pf);
       if (numa && ((r.nr.nflags >> NF_POLICY_SHIFT) & 3u)) aff_v = o.code ? 0 : (int)o.aff;
       if (stamps) atomicMax(&s_ev_max[1], (unsigned int)(__builtin_amdgcn_s_memtime() - e0));
@@ -772,19 +777,20 @@ __global__ void __launch_bounds__(FIX_THREADS) fix_levels_kernel(int16_t* __rest
     atomicAdd(reinterpret_cast<unsigned long long*>(&stamps[11]),
               (unsigned long long)(__builtin_amdgcn_s_memtime() - ct_last));   // kernel start -> every lane evaluated
   }
-  // phase 2: landed entries ranked by (node, index). The patched scores go out at the end of the kernel: vmcnt counts
-  // stores too, and the compiler's vmcnt(0) before the ranking made the stores' round trip part of the chain
+  // phase 2: the 128 threads' entries ranked by (node, index), threads without a landed row last. The patched scores go
+  // out at the end of the kernel: vmcnt counts stores too, and the compiler's vmcnt(0) before the ranking made the
+  // stores' round trip part of the chain
   if (t < 128) {   // waves 0-1: the 128 keys in two registers per lane, compared through readlane (no LDS per key)
-    const uint32_t x = t < npr ? p_raw[t] : 0u;
-    const uint32_t k0 = lane < npr ? p_raw[lane] : 0u, k1 = 64 + lane < npr ? p_raw[64 + lane] : 0u;
+    const uint32_t x = p_raw[t];
+    const uint32_t k0 = p_raw[lane], k1 = p_raw[64 + lane];
     int rank = 0;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
       const uint32_t y0 = __builtin_amdgcn_readlane(k0, i), y1 = __builtin_amdgcn_readlane(k1, i);
-      rank += (i < npr && (y0 < x || (y0 == x && i < t))) ? 1 : 0;
-      rank += (64 + i < npr && (y1 < x || (y1 == x && 64 + i < t))) ? 1 : 0;
+      rank += ((y0 < x || (y0 == x && i < t))) ? 1 : 0;
+      rank += ((y1 < x || (y1 == x && 64 + i < t))) ? 1 : 0;
     }
-    if (t < npr) p_sidx[rank] = t;
+    p_sidx[rank] = t;
   }
   __syncthreads();
   // the first entry of each node, in node order: the distinct landed rows, moved in the histogram
@@ -792,11 +798,9 @@ __global__ void __launch_bounds__(FIX_THREADS) fix_levels_kernel(int16_t* __rest
   int idx = 0, wpre = 0;
   uint32_t xs = 0;
   if (t < 2 * 64) {
-    if (t < npr) {
-      idx = p_sidx[t];
-      xs = p_raw[idx];
-      keep = xs != 0xffffffffu && (t == 0 || p_raw[p_sidx[t - 1]] != xs);
-    }
+    idx = p_sidx[t];
+    xs = p_raw[idx];
+    keep = xs != 0xffffffffu && (t == 0 || p_raw[p_sidx[t - 1]] != xs);
     const uint64_t m = __ballot(keep);
     wpre = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) s_wd[t >> 6] = __popcll(m);
@@ -2049,7 +2053,8 @@ void set_cand_stamps(uint64_t* p) { g_cand_stamps = p; }
 
 hipError_t launch_fix_levels(int16_t* S, uint32_t ld, int npods, int max_score, int lcap, uint32_t* lists,
                              LevelHdr* hdrs, LevelExt* ext, const CandPatch& cp, hipStream_t st) {
-  if (lcap < 1 || lcap > LCAP || !cp.hist || max_score < 0 || max_score > MAX_SCORE_LIMIT || npods > MAX_BATCH)
+  if (lcap < 1 || lcap > LCAP || !cp.hist || !cp.landed || max_score < 0 ||
+      max_score > MAX_SCORE_LIMIT || npods > MAX_BATCH)
     return hipErrorInvalidValue;
   const size_t smem = ((size_t)max_score + 1 + (size_t)lcap) * 4 + (size_t)max_score + 1;
   hipLaunchKernelGGL(fix_levels_kernel, dim3(npods), dim3(FIX_THREADS), smem, st, S, ld, max_score, lcap, lists, hdrs, ext,
@@ -2058,16 +2063,19 @@ hipError_t launch_fix_levels(int16_t* S, uint32_t ld, int npods, int max_score, 
 }
 
 
+size_t landed_slab_bytes() { return LANDED_ROWS + (size_t)MAX_BATCH * sizeof(Row); }
+
 size_t cand_split_scratch_bytes() {
   return (size_t)4 * CS_MAXB * CS_GMAX * (MAX_SCORE_LIMIT + 1 + LEVALL);
 }
 
 hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int npods, int max_score, int lcap,
                        uint32_t* lists, LevelHdr* hdrs, LevelExt* ext, hipStream_t st, const CandPatch* patch,
-                       uint32_t* split_scratch) {
+                       uint32_t* split_scratch, int32_t* tb_written) {
   if (lcap < 1 || lcap > LCAP) return hipErrorInvalidValue;
   CandPatch cp{};
   if (patch) cp = *patch;
+  if (tb_written) *tb_written = 0;
   const uint32_t lenv = (len + 511) & ~511u;
   if (split_scratch && !cp.on && !cp.hist && cp.extra == 0 && !g_cand_stamps && npods >= 1 &&
       npods <= CS_MAXB && max_score >= 0 && max_score <= MAX_SCORE_LIMIT && lenv >= 2 * 2048) {
@@ -2088,6 +2096,7 @@ hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int n
   }
   hipLaunchKernelGGL(cand_kernel, dim3(npods), dim3(64 * CAND_WAVES), cand_smem_bytes(max_score), st, S, ld, len, n0,
                      max_score, lcap, lists, hdrs, ext, g_cand_stamps, cp);
+  if (tb_written && cp.tb) *tb_written = 1;
   return hipGetLastError();
 }
 
