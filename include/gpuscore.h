@@ -382,7 +382,9 @@ int gs_set_now(gs_ctx* ctx, int64_t now_unix_ns);
 /* Node snapshot rows: [upstream] internal/cache Cache.UpdateSnapshot -> NodeInfo (Allocatable, Requested,
  * NonZeroRequested, Pods) plus the node annotations read by EstimateNode
  * (loadaware/estimator/default_estimator.go:110-129) and generateUsageThresholdsFilterProfile (loadaware/helper.go:102-140).
- * Only the given rows are recomputed and copied to HBM. */
+ * Only the given rows are recomputed and copied to HBM. Quantities lie in [0, 2^53) (the exact range of the per-pair
+ * arithmetic): GS_EUNSUPPORTED beyond it or for a negative allocatable, GS_EINVAL for a negative requested /
+ * nonzero_requested (NodeInfo sums pod requests: never negative). */
 int gs_nodes_upsert(gs_ctx* ctx, const uint32_t* idx, const gs_node* nodes, uint32_t n);
 
 /* NodeMetric informer events (lister reads at loadaware/load_aware.go:133,278). pod_metrics holds the

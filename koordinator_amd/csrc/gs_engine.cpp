@@ -714,6 +714,12 @@ int validate_node(gs_ctx* c, const gs_node& n) {
   if (!in_range(n.nonzero_requested[0]) || !in_range(n.nonzero_requested[1]) || !in_range(n.raw_allocatable[0]) ||
       !in_range(n.raw_allocatable[1]) || n.raw_allocatable[0] < 0 || n.raw_allocatable[1] < 0)
     return fail(c, GS_EUNSUPPORTED, "node quantity outside the exact range [0, 2^53)");
+  // NodeInfo.Requested / NonZeroRequested are sums of pod requests: never negative. A negative one would put the
+  // scored quantity above the capacity, outside the per-pair division's range (pct_floor: 0 <= x <= cap)
+  for (int s = 0; s < GS_NUM_RES; ++s)
+    if (n.requested[s] < 0) return fail(c, GS_EINVAL, "node requested of resource slot %d is negative", s);
+  if (n.nonzero_requested[0] < 0 || n.nonzero_requested[1] < 0)
+    return fail(c, GS_EINVAL, "node nonzero_requested is negative");
   if (n.allocatable[GS_RES_RESERVED] || n.requested[GS_RES_RESERVED])
     return fail(c, GS_EINVAL, "resource slot 7 is reserved");
   return GS_OK;
@@ -771,6 +777,11 @@ int validate_pod_msg(bool numa_on, const gs_pod& p, char* msg, size_t len) {
   for (int s = 0; s < GS_NUM_RES; ++s)
     if (!in_range(p.requests[s]) || p.requests[s] < 0 || !in_range(p.limits[s]) || p.limits[s] < 0) {
       snprintf(msg, len, "pod resource slot %d outside the exact range [0, 2^53)", s);
+      return GS_EUNSUPPORTED;
+    }
+  for (int r = 0; r < 2; ++r)   // (the quantity Fit's score subtracts from the node's free non-zero request)
+    if (!in_range(p.nonzero_requests[r]) || p.nonzero_requests[r] < 0) {
+      snprintf(msg, len, "pod nonzero_requests[%d] outside the exact range [0, 2^53)", r);
       return GS_EUNSUPPORTED;
     }
   if (p.requests[GS_RES_RESERVED] || (p.request_mask & 0x80u)) {
@@ -1152,7 +1163,13 @@ int compute_profile(gs_ctx* c) {
   pf.w_fit = (int32_t)cfg.plugin_weights[GS_PLUGIN_FIT];
   pf.w_la = (int32_t)cfg.plugin_weights[GS_PLUGIN_LOADAWARE];
   for (int r = 0; r < 2; ++r) {
-    if (cfg.loadaware.resource_weights_mask & (1u << r)) pf.la_w[r] = (int32_t)cfg.loadaware.resource_weights[r];
+    if (cfg.loadaware.resource_weights_mask & (1u << r)) {
+      // validateResourceWeights (validation_pluginargs.go:61-70): a present key is in (0, 100]; the weighted mean's
+      // division (small_div) is exact for sums below 2^24 only
+      const int64_t w = cfg.loadaware.resource_weights[r];
+      if (w <= 0 || w > 100) return fail(c, GS_EINVAL, "LoadAwareScheduling resource weight %d not in (0, 100]", r);
+      pf.la_w[r] = (int32_t)w;
+    }
     pf.la_wsum += pf.la_w[r];
   }
   for (int s = 0; s < 7; ++s) {

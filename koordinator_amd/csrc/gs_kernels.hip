@@ -1215,6 +1215,12 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
     if (tid == 0) { a.committed[0] = -1; a.committed[1] = 0; a.committed[3] = 0; a.committed[4] = 0; }
     return;
   }
+  // several ranks (node sampling over the score-row exchange): the ranks' blocks are not the same exchange
+  // (unpack_scores_kernel's verdict): commit nothing, and void a speculative pass queued behind (committed[1] = 0)
+  if (a.xerr && a.xerr[0]) {
+    if (tid == 0) { a.committed[0] = 0; a.committed[1] = 0; a.committed[2] = 0; a.committed[3] = COMMIT_ERR_XTAG; a.committed[4] = 0; }
+    return;
+  }
 
   __shared__ uint32_t s_start;                         // nextStartNodeIndex (node sampling)
   __shared__ int32_t s_wred[3][COMMIT_WAVES];                     // window selection: block scans / reductions

@@ -126,6 +126,22 @@ def test_sampling_on_several_ranks_score_rows(n, pct):
     assert want["feasible"].max() == orc.num_feasible_nodes_to_find(4000, pct)
 
 
+def test_sampling_on_several_ranks_diverged_exchange_fails(monkeypatch):
+    """Node sampling on several ranks runs the lockstep commit kernel: it too reads the verdict on the all-gathered
+    blocks' exchange tags. A rank whose exchange sequence diverges (GS_DEBUG_XCHG_SKEW=1:1: rank 1 skips a sequence
+    number at batch 1) fails every rank with GS_ECOMM naming the batch; nothing is committed on mismatched rows."""
+    from tests.test_gpu_parity import run_ranks_local
+    c = synth.make_cluster(3001, 300, 13)
+    cfg = config.make_config(c.num_nodes, percentage_of_nodes_to_score=10)
+    monkeypatch.delenv("GS_XCHG", raising=False)   # the score-row exchange (the default)
+    monkeypatch.setenv("GS_DEBUG_XCHG_SKEW", "1:1")
+    res, _, _ = run_ranks_local(c, cfg, 2)
+    for r in range(2):
+        assert isinstance(res[r], Exception), (r, res[r])
+        msg = str(res[r])
+        assert f"rc={abi.GS_ECOMM}" in msg and "exchange sequence diverged" in msg and "batch 1" in msg, (r, msg)
+
+
 @pytest.mark.parametrize("kind", ["homogeneous", "loaded"])
 def test_sampling_window_spans_several_passes(kind):
     """Windows longer than one 4096-position pass of the commit kernel: the scan continues across passes and the
