@@ -31,6 +31,7 @@
 #include "gs_ext.h"
 #include "gs_kernels.h"
 #include "gs_numa_host.h"
+#include "gs_owned.h"
 
 using namespace gs;
 
@@ -70,6 +71,34 @@ Vec2 usage_of(const gs_usage& u) {
   if (u.mask & GS_USAGE_OTHER) o.mask |= GS_USAGE_OTHER;
   return o;
 }
+
+// One of the two per-batch buffer sets: everything a batch in flight reads or writes on its own. While one slot's batch
+// commits, the next batch is staged and enqueued speculatively on the other slot (schedule_stream).
+struct Slot {
+  Event ev_go, ev_evdone;
+  Event ev[6];                      // timing marks: eval start [0] / end [1], forced commit [3], commit end [4]; [5] readback
+  bool untimed = false;             // the batch recorded no timing events (a short direct batch)
+  DevBuf<int16_t> d_S;              // score rows of the slot's batch
+  DevBuf<uint8_t> d_aff;            // [pod][ld] Filter-time NUMA affinity of policy nodes (eval -> commit Reserve)
+  // pods | seq and committed | out share one allocation each (device and pinned host): one copy per batch each way
+  DevBuf<PodVec> d_pods;
+  PinnedBuf<PodVec> h_pods;
+  DevBuf<int32_t> d_committed;
+  PinnedBuf<int32_t> h_committed;
+  DevBuf<uint8_t> d_lst;            // overlapped cand (one shard): the slot's lists + headers, and its histograms
+  DevBuf<uint32_t> d_hist;
+  DevBuf<uint8_t> d_landed;         // the landed slab the slot's commit leaves for the next batch's fix-up (cand_overlap)
+  // Views, not owners: seq behind the slot's pods and out behind its committed words; the slot's part of gs_ctx's
+  // tb_all (gs_create) and of its sx_send_all, sx_recv_all and d_xerr (alloc_exchange)
+  uint64_t *d_seq = nullptr, *h_seq = nullptr;
+  PlacementDev *d_out = nullptr, *h_out = nullptr;
+  int32_t* d_tb = nullptr;          // the slot's tie-break records: cand_kernel writes the next batch's beside this commit
+  uint8_t* d_sx_send = nullptr;     // score-row exchange: [B x pld int16 | B x pld u8 | ... | XTag]
+  uint8_t* d_sx_recv = nullptr;     // R blocks
+  // the verdict on the batch's exchange tags (score rows: the slot's own, written by unpack_scores_kernel; levels:
+  // merge_levels_kernel's, one block for both slots; one rank: none)
+  int32_t* d_xerr = nullptr;
+};
 
 }  // namespace
 
@@ -131,80 +160,48 @@ struct gs_local_group {
   }
 };
 
+// Members are destroyed in reverse order: the buffers go first, then the events, then the streams (gs_destroy).
 struct gs_ctx {
+  Stream st;
+  Stream st2;                               // side stream: eval_kernel beside eval_numa_kernel
+  Stream st_ev;                             // eval passes: a batch's eval runs beside the previous batch's commit
+  Stream st_rb;                             // a batch's placement readback, off the stream the next batch runs on
+  Event ev_fork, ev_join;
+  std::vector<Event> x_ev;                  // RCCL all-gather start / end events not yet accounted (exchange_ms)
+  int x_pending = 0;
+  Event lg_ready, lg_done;                  // in-process device transport: this rank's events of an exchange
+  // double-buffered per-batch state: the next batch is enqueued speculatively before the current one is read back
+  // (gs_schedule). cur_slot: the slot whose batch is current; between runs its buffers serve as scratch (current_slot)
+  Slot slot[2];
+  int cur_slot = 0;
   std::unordered_set<uint64_t> ext_reserved;   // pods placed with an extension-path Reserve (gs_schedule_ext)
   gs_config cfg{};
   std::string err;
   std::unique_ptr<AsyncQueue> aq;   // gs_schedule_submit's worker (created by the first submission)
   uint32_t N = 0, npad = 0;
-  hipStream_t st = nullptr;
-  hipStream_t st2 = nullptr;                // side stream: eval_kernel beside eval_numa_kernel
-  hipStream_t st_ev = nullptr;              // eval passes: a batch's eval runs beside the previous batch's commit
-  hipStream_t st_rb = nullptr;              // a batch's placement readback, off the stream the next batch runs on
   uint32_t window_k = 0;                    // node sampling: numFeasibleNodesToFind(N) (0 = every node)
   uint32_t next_start = 0;                  // [upstream] Scheduler.nextStartNodeIndex
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  std::vector<hipEvent_t> x_ev;             // RCCL all-gather start / end events not yet accounted (exchange_ms)
-  int x_pending = 0;
-  // device mirror
-  int64_t* d_i64 = nullptr;
-  int32_t* d_i32 = nullptr;
+  // device mirror (mv: views of the two)
+  DevBuf<int64_t> mirror_i64;
+  DevBuf<int32_t> mirror_i32;
   MirrorView mv{};
   // batch buffers
   int B = MAX_BATCH;
-  PodVec* d_pods = nullptr;
-  uint64_t* d_seq = nullptr;
-  int16_t* d_S = nullptr;
   uint32_t ld = 0;
-  uint8_t* d_xchg_send = nullptr;   // local lists + headers (contiguous, all-gathered)
-  uint8_t* d_xchg_recv = nullptr;   // R blocks
-  uint8_t* d_xmerged = nullptr;     // several ranks, speculative commit: the R blocks' levels merged into one block
+  DevBuf<uint8_t> d_xchg_send;      // local lists + headers (contiguous, all-gathered)
+  DevBuf<uint8_t> d_xchg_recv;      // R blocks
+  DevBuf<uint8_t> d_xmerged;        // several ranks, speculative commit: the R blocks' levels merged into one block
   size_t xchg_bytes = 0;
   int lstride = LCAP;               // listed nodes per pod in the local / exchanged blocks (XCAP: several ranks, spec)
-  PlacementDev* d_out = nullptr;
-  int32_t* d_committed = nullptr;
-  int32_t* d_tb = nullptr;          // speculative commit: tie-break records of the batch's pods (the bound slot's)
-  RowStat* d_rowstat = nullptr;
-  int32_t* d_sel = nullptr;
-  uint32_t* d_stage_idx = nullptr;
-  int64_t* d_stage_rows = nullptr;
+  DevBuf<int32_t> tb_all;           // speculative commit: tie-break records of the batches' pods, both slots' (Slot::d_tb)
+  DevBuf<RowStat> d_rowstat;
+  DevBuf<int32_t> d_sel;
+  DevBuf<int64_t> d_stage_rows;     // flush_rows staging (device / pinned): rows, then their node indices
+  PinnedBuf<int64_t> h_stage_rows;
   uint32_t stage_cap = 0;
-  // pinned host buffers
-  PodVec* h_pods = nullptr;
-  uint64_t* h_seq = nullptr;
-  PlacementDev* h_out = nullptr;
-  int32_t* h_committed = nullptr;
-  uint32_t* h_stage_idx = nullptr;
-  int64_t* h_stage_rows = nullptr;
-  uint8_t* h_xchg_send = nullptr;
-  uint8_t* h_xchg_recv = nullptr;
-  hipEvent_t ev[8] = {};
-  // double-buffered per-batch buffers (slot 0 = the fields above when bound): the next batch is enqueued
-  // speculatively before the current one is read back (gs_schedule)
-  struct Slot {
-    int16_t* d_S = nullptr;         // score rows and Filter-time affinities of the slot's batch
-    uint8_t* d_aff = nullptr;
-    hipEvent_t ev_go = nullptr, ev_evdone = nullptr;
-    PodVec* d_pods = nullptr;
-    uint64_t* d_seq = nullptr;
-    PlacementDev* d_out = nullptr;
-    int32_t* d_committed = nullptr;
-    PodVec* h_pods = nullptr;
-    uint64_t* h_seq = nullptr;
-    PlacementDev* h_out = nullptr;
-    int32_t* h_committed = nullptr;
-    hipEvent_t ev[6] = {};
-    bool untimed = false;           // the batch recorded no timing events (a short direct batch)
-    uint8_t* d_lst = nullptr;       // overlapped cand (one shard): the slot's lists + headers, and its histograms
-    uint32_t* d_hist = nullptr;
-    int32_t* d_tb = nullptr;        // the slot's tie-break records: cand_kernel writes the next batch's beside this commit
-    uint8_t* d_landed = nullptr;    // the landed slab the slot's commit leaves for the next batch's fix-up (cand_overlap)
-  } slot[2];
+  PinnedBuf<uint8_t> h_xchg_send, h_xchg_recv;   // host-callback transport
   bool cand_overlap = false;        // GS_CAND_OVERLAP (default on): cand beside the previous commit, fix_levels after it
-  uint8_t* d_lst = nullptr;         // the bound slot's (cand_overlap)
-  uint32_t* d_hist = nullptr;
-  uint32_t* d_cscratch = nullptr;   // launch_cand's short-batch split (slice histograms, slice offsets)
-  int cur_slot = 0;
+  DevBuf<uint32_t> d_cscratch;      // launch_cand's short-batch split (slice histograms, slice offsets)
   // host mirror
   std::vector<HostNode> nodes;
   std::vector<uint8_t> row_dirty;
@@ -225,22 +222,19 @@ struct gs_ctx {
   uint32_t e0 = 0, e1 = 0;          // the node range this rank evaluates
   uint32_t sx_per = 0, sx_pld = 0;  // nodes per shard, the block's row stride
   size_t sx_bytes = 0;              // one rank's score block (tag included)
-  uint8_t* d_sx_send = nullptr;     // [B x pld int16 | B x pld u8 | ... | XTag]
-  uint8_t* d_sx_recv = nullptr;     // R blocks
-  uint8_t* h_sx_send = nullptr;     // host-callback transport
-  uint8_t* h_sx_recv = nullptr;
+  DevBuf<uint8_t> sx_send_all, sx_recv_all;   // both slots' send blocks (Slot::d_sx_send), R-block sets (d_sx_recv)
+  PinnedBuf<uint8_t> h_sx_send, h_sx_recv;    // host-callback transport
   uint32_t n_valid = 0;   // nodes upserted at least once (ready())
   ncclComm_t comm = nullptr;
   gs_allgather_fn cb = nullptr;
   void* cb_user = nullptr;
   gs_local_group* lg = nullptr;     // in-process device transport (tests: ranks as threads)
-  hipEvent_t lg_ready = nullptr, lg_done = nullptr;
   // exchange sequence (XTag): every exchange's block carries (site, seq, batch, rank); all ranks check all tags
   std::atomic<uint64_t> xseq{0};    // exchanges so far
   std::atomic<uint64_t> xbatch{0};  // batch passes launched so far (launch_batch)
-  int32_t* d_xerr = nullptr;        // merge_levels_kernel's verdict on the level blocks' tags
-  uint8_t* d_xsmall = nullptr;      // small exchanges (row stats, selection): [own block | R blocks] of XSMALL bytes
-  uint8_t* h_xsmall = nullptr;      // their R blocks read back
+  DevBuf<int32_t> d_xerr;           // the tag verdicts of unpack_scores_kernel / merge_levels_kernel (Slot::d_xerr)
+  DevBuf<uint8_t> d_xsmall;         // small exchanges (row stats, selection): [own block | R blocks] of XSMALL bytes
+  PinnedBuf<uint8_t> h_xsmall;      // their R blocks read back
   int64_t dbg_xskew_rank = -1;      // GS_DEBUG_XCHG_SKEW=rank:batch (tests): that rank skips one sequence number there
   uint64_t dbg_xskew_batch = 0;
   // GS_WATCHDOG_S=<seconds> (diagnostics): a thread reports on stderr any host wait of the scheduling path that lasts
@@ -250,7 +244,7 @@ struct gs_ctx {
   std::thread watchdog;
   std::atomic<bool> wd_stop{false};
   gs_stats stats{};
-  uint64_t* d_stamps = nullptr;   // GS_COMMIT_STAMPS=1: commit-kernel phase cycle sums
+  DevBuf<uint64_t> d_stamps;      // GS_COMMIT_STAMPS=1: commit-kernel phase cycle sums
   uint64_t stats_all_pods = 0;     // pods placed by gs_schedule over the context's life (stamp averages)
   // GS_HOST_TIMING=1: host time per batch of schedule_stream, by phase (printed by gs_destroy)
   bool host_timing = false;
@@ -267,22 +261,23 @@ struct gs_ctx {
   std::unordered_map<uint64_t, uint32_t> numa_uid_node;   // pods holding a NodeAllocation record
   bool numa_on = false;
   // the shard's nodes with a NUMA topology policy (eval_numa_kernel's work list), rebuilt when policies change
-  uint32_t* d_numa_idx = nullptr;
+  DevBuf<uint32_t> d_numa_idx;
   uint32_t numa_n = 0;
-  MirrorView slab_mv{nullptr, nullptr, 0};   // the eval pass's dense copy of the NUMA-policy rows (gather_numa_kernel)
+  DevBuf<int64_t> slab_i64;                  // the eval pass's dense copy of the NUMA-policy rows (gather_numa_kernel)
+  DevBuf<int32_t> slab_i32;
+  MirrorView slab_mv{nullptr, nullptr, 0};   // (views of the two)
   uint32_t slab_cap = 0;
   bool numa_idx_stale = true;
   // the extension path's list over [n0, n1) (all nodes under the score-row exchange, where the batch path's list covers
   // the rank's shard only): its own buffer, so pods alternating between the two paths rebuild neither
-  uint32_t* d_xnuma_idx = nullptr;
+  DevBuf<uint32_t> d_xnuma_idx;
   uint32_t xnuma_n = 0;
   bool xnuma_stale = true;
   uint32_t numa_idx_lo = 0, numa_idx_hi = 0;   // the node range d_numa_idx lists (the batch path's shard [e0, e1))
   int64_t prep_now = INT64_MIN;             // `now` of the last full node_prep pass
   // registered topologies in bit-plane form (the commit kernel's cpuset Reserve), and the host re-check of
   // every device-chosen cpuset (GS_VERIFY_CPUSET=1)
-  TopoDev* d_topos = nullptr;
-  uint8_t* d_aff = nullptr;       // [pod][ld] Filter-time NUMA affinity of policy nodes (eval -> commit Reserve)
+  DevBuf<TopoDev> d_topos;
   bool verify_cpuset = false;
   // Reservation + DeviceShare (gs_ext.hip): host mirror of the nodes' GPU devices and of the reservation cache
   gs_ext_args ext{};
@@ -292,25 +287,25 @@ struct gs_ctx {
   std::map<uint64_t, gs_reservation> rsv;        // reservationCache by uid (uid order = the harness's iteration order)
   std::vector<std::vector<uint64_t>> rsv_node;   // uids per node, ascending
   std::unordered_map<uint64_t, std::vector<uint64_t>> rsv_owner;   // owner key -> uids
-  DevNode* d_dev = nullptr;
-  DevNode* h_dev_stage = nullptr;   // ext_flush_devices staging (pinned / device): images, then node indices
-  DevNode* d_dev_stage = nullptr;
+  DevBuf<DevNode> d_dev;
+  PinnedBuf<DevNode> h_dev_stage;   // ext_flush_devices staging (pinned / device): images, then node indices
+  DevBuf<DevNode> d_dev_stage;
+  DevBuf<int32_t> d_xtot;
+  DevBuf<int16_t> d_xds, d_xrs;
+  DevBuf<int32_t> d_xnom;
+  DevBuf<int32_t> d_xT;
+  DevBuf<ExtOut> d_xout;
+  PinnedBuf<unsigned char> h_xin;    // one extension pod's inputs, staged for ONE copy: ExtPod | PodVec | ExtRec[] |
+  DevBuf<unsigned char> d_xin;       // ExtRes[] (pinned host / device, ext_stage_layout)
+  // views into h_xin / d_xin (ext_stage_reserve): the sections of the staged block
+  ExtPod* h_xpod = nullptr;
   ExtPod* d_xpod = nullptr;
+  PodVec* d_xpv = nullptr;
   ExtRec* d_xrec = nullptr;
   ExtRes* d_xres = nullptr;
-  int32_t* d_xtot = nullptr;
-  int16_t* d_xds = nullptr;
-  int16_t* d_xrs = nullptr;
-  int32_t* d_xnom = nullptr;
-  int32_t* d_xT = nullptr;
-  ExtOut* d_xout = nullptr;
-  ExtPod* h_xpod = nullptr;          // (the host half of d_xin's first section)
-  unsigned char* h_xin = nullptr;    // one extension pod's inputs, staged for ONE copy: ExtPod | PodVec | ExtRec[] |
-  unsigned char* d_xin = nullptr;    // ExtRes[] (pinned host / device, ext_stage_layout)
-  PodVec* d_xpv = nullptr;
   size_t xin_off_rec = 0, xin_off_res = 0, xin_bytes = 0;
-  ExtOut* h_xout = nullptr;
-  int32_t* h_xnom = nullptr;
+  PinnedBuf<ExtOut> h_xout;
+  PinnedBuf<int32_t> h_xnom;
   std::vector<ExtRec> xrec;
   std::vector<ExtRes> xres;
   std::vector<uint64_t> xres_uid;
@@ -320,6 +315,10 @@ struct gs_ctx {
 int quiesce(gs_ctx* c);   // the async submissions' worker is idle (gs_schedule_submit)
 
 namespace {
+// The slot whose batch is current. Between runs no batch is in flight: gs_evaluate and the extension path borrow its
+// buffers and events as scratch, whichever of the two slots the last run ended on.
+Slot& current_slot(gs_ctx* c) { return c->slot[c->cur_slot]; }
+
 int64_t mono_ns() {
   return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -385,13 +384,13 @@ void watchdog_loop(gs_ctx* c, double limit_s) {
     // which device work is still pending: the streams, and per batch slot its eval-pass end (evdone), commit end
     // (ev[4]) and readback end (ev[5]) (0 = complete, 1 = pending)
     auto q = [](hipError_t e) { return e == hipSuccess ? 0 : e == hipErrorNotReady ? 1 : 9; };
+    auto qe = [&](const Event& ev) { return q(hipEventQuery(ev.get())); };
+    const Slot &s0 = c->slot[0], &s1 = c->slot[1];
     fprintf(stderr, "gpuscore watchdog: rank %d of %d blocked %.1f s in %s (batch pass %llu, exchange %llu); pending: "
             "st %d st_ev %d st2 %d st_rb %d | slot 0 evdone %d ev4 %d ev5 %d | slot 1 evdone %d ev4 %d ev5 %d (bound %d)\n",
-            c->rank, c->nranks, s, w, (unsigned long long)c->xbatch, (unsigned long long)c->xseq, q(hipStreamQuery(c->st)),
-            q(hipStreamQuery(c->st_ev)), q(hipStreamQuery(c->st2)), q(hipStreamQuery(c->st_rb)),
-            q(hipEventQuery(c->slot[0].ev_evdone)), q(hipEventQuery(c->slot[0].ev[4])), q(hipEventQuery(c->slot[0].ev[5])),
-            q(hipEventQuery(c->slot[1].ev_evdone)), q(hipEventQuery(c->slot[1].ev[4])), q(hipEventQuery(c->slot[1].ev[5])),
-            c->cur_slot);
+            c->rank, c->nranks, s, w, (unsigned long long)c->xbatch, (unsigned long long)c->xseq, q(hipStreamQuery(c->st.get())),
+            q(hipStreamQuery(c->st_ev.get())), q(hipStreamQuery(c->st2.get())), q(hipStreamQuery(c->st_rb.get())), qe(s0.ev_evdone),
+            qe(s0.ev[4]), qe(s0.ev[5]), qe(s1.ev_evdone), qe(s1.ev[4]), qe(s1.ev[5]), c->cur_slot);
     fflush(stderr);
     reported = w;
     reported_t = t;
@@ -824,27 +823,27 @@ int flush_rows(gs_ctx* c) {
     uint32_t n = (uint32_t)std::min<size_t>(c->stage_cap, c->dirty_list.size() - done);
     // staging buffers are reused: the previous scatter must have consumed them
     Where w_(c, "flush_rows: previous scatter");
-    HIP_TRY(c, host_wait_stream(c->st));
+    HIP_TRY(c, host_wait_stream(c->st.get()));
     // one staged block, one copy: the n rows, then their node indices
-    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_stage_rows + (size_t)n * ROW_WORDS);
+    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_stage_rows.get() + (size_t)n * ROW_WORDS);
     for (uint32_t j = 0; j < n; ++j) {
       uint32_t i = c->dirty_list[done + j];
       h_idx[j] = i;
-      derive_row(c, i, c->h_stage_rows + (size_t)j * ROW_WORDS);
-      derive_row_numa(c, i, c->h_stage_rows + (size_t)j * ROW_WORDS);
+      derive_row(c, i, c->h_stage_rows.get() + (size_t)j * ROW_WORDS);
+      derive_row_numa(c, i, c->h_stage_rows.get() + (size_t)j * ROW_WORDS);
       c->row_dirty[i] = 0;
     }
-    HIP_TRY(c, hipMemcpyAsync(c->d_stage_rows, c->h_stage_rows, (size_t)n * (ROW_WORDS * 8 + 4), hipMemcpyHostToDevice,
-                              c->st));
-    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(c->d_stage_rows + (size_t)n * ROW_WORDS);
+    HIP_TRY(c, hipMemcpyAsync(c->d_stage_rows.get(), c->h_stage_rows.get(), (size_t)n * (ROW_WORDS * 8 + 4), hipMemcpyHostToDevice,
+                              c->st.get()));
+    const uint32_t* d_idx = reinterpret_cast<const uint32_t*>(c->d_stage_rows.get() + (size_t)n * ROW_WORDS);
     // with the rows' LoadAware verdicts at `now` (node_prep, fused into the scatter), unless a full pass is due anyway
     if (!c->prep_stale && c->prep_now == c->now) {
       const gs_loadaware_args& la = c->cfg.loadaware;
       const ScatterPrep sp{c->now, la.filter_expired_node_metrics, la.has_node_metric_expiration,
                            la.has_node_metric_expiration ? la.node_metric_expiration_seconds * 1000000000LL : 0};
-      HIP_TRY(c, launch_scatter_rows(c->mv, d_idx, c->d_stage_rows, n, c->st, &sp));
+      HIP_TRY(c, launch_scatter_rows(c->mv, d_idx, c->d_stage_rows.get(), n, c->st.get(), &sp));
     } else {
-      HIP_TRY(c, launch_scatter_rows(c->mv, d_idx, c->d_stage_rows, n, c->st));
+      HIP_TRY(c, launch_scatter_rows(c->mv, d_idx, c->d_stage_rows.get(), n, c->st.get()));
     }
 
     c->stats.delta_rows += n;
@@ -860,7 +859,7 @@ int node_prep(gs_ctx* c) {
   const gs_loadaware_args& a = c->cfg.loadaware;
   int64_t exp_ns = a.has_node_metric_expiration ? a.node_metric_expiration_seconds * 1000000000LL : 0;
   HIP_TRY(c, launch_node_prep(c->mv, 0, c->N, c->now, a.filter_expired_node_metrics, a.has_node_metric_expiration,
-                              exp_ns, c->st));
+                              exp_ns, c->st.get()));
   c->prep_stale = false;
   c->prep_now = c->now;
   return GS_OK;
@@ -889,7 +888,7 @@ double ev_ms(hipEvent_t a, hipEvent_t b) {
 void flush_exchange_times(gs_ctx* c) {
   int keep = 0;
   for (int i = 0; i < c->x_pending; ++i) {
-    hipEvent_t a = c->x_ev[2 * i], b = c->x_ev[2 * i + 1];
+    hipEvent_t a = c->x_ev[2 * i].get(), b = c->x_ev[2 * i + 1].get();
     if (hipEventQuery(b) == hipSuccess) {
       c->stats.exchange_ms += ev_ms(a, b);
     } else {   // still in flight: keep the pair (moved to the front)
@@ -925,16 +924,26 @@ int check_tags(gs_ctx* c, const uint8_t* blocks, size_t bytes, const XTag& mine)
   return GS_OK;
 }
 
+// the start / end event pair of the next device-side exchange (x_ev[2 * x_pending], + 1), created on first use
+int reserve_exchange_events(gs_ctx* c) {
+  while (c->x_pending * 2 + 2 > (int)c->x_ev.size()) {
+    Event ev;
+    HIP_TRY(c, ev.create());
+    c->x_ev.push_back(std::move(ev));
+  }
+  return GS_OK;
+}
+
 // One all-gather of `bytes`-byte blocks (each ending in an XTag, filled here) from d_send into R blocks at d_recv.
 // RCCL: stream-ordered, the tag written on the stream before the collective; the receiver checks the tags (the level
 // blocks on the device in merge_levels_kernel, the small ones on the host). Callback: host-synchronous, checked here.
 int exchange(gs_ctx* c, uint32_t site, uint8_t* d_send, uint8_t* d_recv, size_t bytes, XTag* sent = nullptr,
              hipStream_t xs = nullptr) {
   auto t0 = std::chrono::steady_clock::now();
-  if (!xs) xs = c->st;
+  if (!xs) xs = c->st.get();
   // the host-callback transport's staging: the score blocks have their own buffers
-  uint8_t* h_send = site == XSITE_SCORES ? c->h_sx_send : c->h_xchg_send;
-  uint8_t* h_recv = site == XSITE_SCORES ? c->h_sx_recv : c->h_xchg_recv;
+  uint8_t* h_send = site == XSITE_SCORES ? c->h_sx_send.get() : c->h_xchg_send.get();
+  uint8_t* h_recv = site == XSITE_SCORES ? c->h_sx_recv.get() : c->h_xchg_recv.get();
   const size_t h_cap = site == XSITE_SCORES ? c->sx_bytes : c->xchg_bytes;
   if (bytes < sizeof(XTag) || bytes % 8) return fail(c, GS_EINVAL, "exchange block of %zu bytes", bytes);
   XTag tag{XTAG_MAGIC, site, ++c->xseq, c->xbatch, c->rank, (uint32_t)bytes};
@@ -943,37 +952,25 @@ int exchange(gs_ctx* c, uint32_t site, uint8_t* d_send, uint8_t* d_recv, size_t 
   if (sent) *sent = tag;
   if (c->comm) {
     HIP_TRY(c, launch_write_tag(d_send + bytes - sizeof(XTag), tag, xs));
-    if (c->x_pending * 2 + 2 > (int)c->x_ev.size()) {
-      for (int k = 0; k < 2; ++k) {
-        hipEvent_t ev;
-        HIP_TRY(c, hipEventCreate(&ev));
-        c->x_ev.push_back(ev);
-      }
-    }
-    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending], xs));
+    if (int rc = reserve_exchange_events(c)) return rc;
+    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending].get(), xs));
     ncclResult_t r = ncclAllGather(d_send, d_recv, bytes, ncclUint8, c->comm, xs);
     if (r != ncclSuccess) return fail(c, GS_ECOMM, "ncclAllGather: %s", ncclGetErrorString(r));
-    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending + 1], xs));
+    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending + 1].get(), xs));
     ++c->x_pending;
     return GS_OK;
   } else if (c->lg) {
     gs_local_group& g = *c->lg;
     static const double limit = env_num("GS_LOCAL_WAIT_S", 60.0);
     HIP_TRY(c, launch_write_tag(d_send + bytes - sizeof(XTag), tag, xs));
-    if (c->x_pending * 2 + 2 > (int)c->x_ev.size()) {
-      for (int k = 0; k < 2; ++k) {
-        hipEvent_t ev;
-        HIP_TRY(c, hipEventCreate(&ev));
-        c->x_ev.push_back(ev);
-      }
-    }
-    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending], xs));
-    HIP_TRY(c, hipEventRecord(c->lg_ready, xs));
+    if (int rc = reserve_exchange_events(c)) return rc;
+    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending].get(), xs));
+    HIP_TRY(c, hipEventRecord(c->lg_ready.get(), xs));
     {
       std::lock_guard<std::mutex> lk(g.mu);
       g.send[c->rank] = d_send;
       g.bytes[c->rank] = bytes;
-      g.ready[c->rank] = c->lg_ready;
+      g.ready[c->rank] = c->lg_ready.get();
     }
     bool met;
     {
@@ -990,10 +987,10 @@ int exchange(gs_ctx* c, uint32_t site, uint8_t* d_send, uint8_t* d_recv, size_t 
         HIP_TRY(c, hipStreamWaitEvent(xs, g.ready[s], 0));
         HIP_TRY(c, hipMemcpyAsync(d_recv + (size_t)s * bytes, g.send[s], bytes, hipMemcpyDeviceToDevice, xs));
       }
-    HIP_TRY(c, hipEventRecord(c->lg_done, xs));
+    HIP_TRY(c, hipEventRecord(c->lg_done.get(), xs));
     {
       std::lock_guard<std::mutex> lk(g.mu);
-      g.done[c->rank] = c->lg_done;
+      g.done[c->rank] = c->lg_done.get();
     }
     {
       Where w_(c, "exchange (local transport): the ranks' copies");
@@ -1006,7 +1003,7 @@ int exchange(gs_ctx* c, uint32_t site, uint8_t* d_send, uint8_t* d_recv, size_t 
                            (unsigned long long)tag.seq);
     for (int s = 0; s < c->nranks; ++s)
       if (s != c->rank) HIP_TRY(c, hipStreamWaitEvent(xs, g.done[s], 0));
-    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending + 1], xs));
+    HIP_TRY(c, hipEventRecord(c->x_ev[2 * c->x_pending + 1].get(), xs));
     ++c->x_pending;
     return GS_OK;
   } else if (c->cb) {
@@ -1035,21 +1032,21 @@ int exchange_small(gs_ctx* c, uint32_t site, const void* d_payload, size_t paylo
                    hipStream_t xs = nullptr, const void* host_in = nullptr) {
   static_assert(XSMALL >= 32 + sizeof(XTag), "small exchange block");
   if (payload > XSMALL - sizeof(XTag)) return fail(c, GS_EINVAL, "small exchange payload too large");
-  if (!xs) xs = c->st;
+  if (!xs) xs = c->st.get();
   if (d_payload) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_xsmall, d_payload, payload, hipMemcpyDeviceToDevice, xs));
+    HIP_TRY(c, hipMemcpyAsync(c->d_xsmall.get(), d_payload, payload, hipMemcpyDeviceToDevice, xs));
   } else {   // (h_xsmall is free between small exchanges: staged through it, in stream order)
-    std::memcpy(c->h_xsmall, host_in, payload);
-    HIP_TRY(c, hipMemcpyAsync(c->d_xsmall, c->h_xsmall, payload, hipMemcpyHostToDevice, xs));
+    std::memcpy(c->h_xsmall.get(), host_in, payload);
+    HIP_TRY(c, hipMemcpyAsync(c->d_xsmall.get(), c->h_xsmall.get(), payload, hipMemcpyHostToDevice, xs));
   }
   XTag tag{};
-  if (int rc = exchange(c, site, c->d_xsmall, c->d_xsmall + XSMALL, XSMALL, &tag, xs)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(c->h_xsmall, c->d_xsmall + XSMALL, XSMALL * c->nranks, hipMemcpyDeviceToHost, xs));
+  if (int rc = exchange(c, site, c->d_xsmall.get(), c->d_xsmall.get() + XSMALL, XSMALL, &tag, xs)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_xsmall.get(), c->d_xsmall.get() + XSMALL, XSMALL * c->nranks, hipMemcpyDeviceToHost, xs));
   Where w_(c, "exchange_small: read back");
   HIP_TRY(c, host_wait_stream(xs));
-  if (int rc = check_tags(c, c->h_xsmall, XSMALL, tag)) return rc;
+  if (int rc = check_tags(c, c->h_xsmall.get(), XSMALL, tag)) return rc;
   for (int r = 0; r < c->nranks; ++r)
-    std::memcpy(static_cast<uint8_t*>(host_out) + (size_t)r * payload, c->h_xsmall + (size_t)r * XSMALL, payload);
+    std::memcpy(static_cast<uint8_t*>(host_out) + (size_t)r * payload, c->h_xsmall.get() + (size_t)r * XSMALL, payload);
   return GS_OK;
 }
 
@@ -1225,48 +1222,41 @@ int alloc_exchange(gs_ctx* c) {
   // (score rows: every rank runs the one-shard pipeline over all nodes, LCAP-wide local lists)
   c->lstride = !c->sgather && commit_spec_selected(c->window_k) ? XCAP : LCAP;
   c->xchg_bytes = xchg_block_bytes(c->B, c->lstride);
-  if (c->d_xchg_recv) { (void)hipFree(c->d_xchg_recv); c->d_xchg_recv = nullptr; }
-  if (c->h_xchg_recv) { (void)hipHostFree(c->h_xchg_recv); c->h_xchg_recv = nullptr; }
-  HIP_TRY(c, hipMalloc(&c->d_xchg_recv, c->xchg_bytes * c->nranks + 64));
-  HIP_TRY(c, hipHostMalloc(&c->h_xchg_recv, c->xchg_bytes * c->nranks + 64, hipHostMallocDefault));
-  if (c->d_xmerged) { (void)hipFree(c->d_xmerged); c->d_xmerged = nullptr; }
-  HIP_TRY(c, hipMalloc(&c->d_xmerged, xchg_block_bytes(c->B, LCAP) + 64));
-  if (!c->d_xerr) HIP_TRY(c, hipMalloc(&c->d_xerr, 2 * XERR_BYTES));   // one per batch slot (score rows)
-  HIP_TRY(c, hipMemset(c->d_xerr, 0, 2 * XERR_BYTES));
-  if (c->d_sx_send) { (void)hipFree(c->d_sx_send); c->d_sx_send = nullptr; }
-  if (c->d_sx_recv) { (void)hipFree(c->d_sx_recv); c->d_sx_recv = nullptr; }
-  if (c->h_sx_send) { (void)hipHostFree(c->h_sx_send); c->h_sx_send = nullptr; }
-  if (c->h_sx_recv) { (void)hipHostFree(c->h_sx_recv); c->h_sx_recv = nullptr; }
+  // (alloc() frees the old block first, here and below: comm init runs after quiesce, with no batch in flight)
+  HIP_TRY(c, c->d_xchg_recv.alloc(c->xchg_bytes * c->nranks + 64));
+  HIP_TRY(c, c->h_xchg_recv.alloc(c->xchg_bytes * c->nranks + 64));
+  HIP_TRY(c, c->d_xmerged.alloc(xchg_block_bytes(c->B, LCAP) + 64));
+  if (!c->d_xerr) HIP_TRY(c, c->d_xerr.alloc(2 * XERR_BYTES));   // one per batch slot (score rows)
+  HIP_TRY(c, hipMemset(c->d_xerr.get(), 0, 2 * XERR_BYTES));
+  c->sx_send_all.reset();
+  c->sx_recv_all.reset();
+  c->h_sx_send.reset();
+  c->h_sx_recv.reset();
+  for (Slot& sl : c->slot) sl.d_sx_send = sl.d_sx_recv = nullptr;
   c->sx_bytes = 0;
   if (c->sgather) {
     c->sx_bytes = ((size_t)c->B * c->sx_pld * 3 + sizeof(XTag) + 255) / 256 * 256;
-    HIP_TRY(c, hipMalloc(&c->d_sx_send, c->sx_bytes * 2));               // one per batch slot
-    HIP_TRY(c, hipMalloc(&c->d_sx_recv, c->sx_bytes * c->nranks * 2));
+    HIP_TRY(c, c->sx_send_all.alloc(c->sx_bytes * 2));               // one per batch slot
+    HIP_TRY(c, c->sx_recv_all.alloc(c->sx_bytes * c->nranks * 2));
     if (c->cb) {
-      HIP_TRY(c, hipHostMalloc(&c->h_sx_send, c->sx_bytes, hipHostMallocDefault));
-      HIP_TRY(c, hipHostMalloc(&c->h_sx_recv, c->sx_bytes * c->nranks, hipHostMallocDefault));
+      HIP_TRY(c, c->h_sx_send.alloc(c->sx_bytes));
+      HIP_TRY(c, c->h_sx_recv.alloc(c->sx_bytes * c->nranks));
+    }
+    for (int k = 0; k < 2; ++k) {
+      c->slot[k].d_sx_send = c->sx_send_all.get() + c->sx_bytes * k;
+      c->slot[k].d_sx_recv = c->sx_recv_all.get() + c->sx_bytes * c->nranks * k;
     }
   }
-  if (!c->d_xsmall) HIP_TRY(c, hipMalloc(&c->d_xsmall, XSMALL * (1 + MAX_RANKS)));
-  if (!c->h_xsmall) HIP_TRY(c, hipHostMalloc(&c->h_xsmall, XSMALL * MAX_RANKS, hipHostMallocDefault));
+  for (int k = 0; k < 2; ++k)
+    c->slot[k].d_xerr = c->sgather ? c->d_xerr.get() + (XERR_BYTES / 4) * k : c->nranks > 1 ? c->d_xerr.get() : nullptr;
+  if (!c->d_xsmall) HIP_TRY(c, c->d_xsmall.alloc(XSMALL * (1 + MAX_RANKS)));
+  if (!c->h_xsmall) HIP_TRY(c, c->h_xsmall.alloc(XSMALL * MAX_RANKS));
   if (const char* sk = env_str("GS_DEBUG_XCHG_SKEW")) {   // "rank:batch" (tests of the sequence check)
     long r = -1;
     unsigned long long b = 0;
     if (sscanf(sk, "%ld:%llu", &r, &b) == 2) { c->dbg_xskew_rank = r; c->dbg_xskew_batch = b; }
   }
   return GS_OK;
-}
-
-
-void bind_slot(gs_ctx* c, int s) {
-  const gs_ctx::Slot& x = c->slot[s];
-  c->d_S = x.d_S; c->d_aff = x.d_aff;
-  c->d_pods = x.d_pods; c->d_seq = x.d_seq; c->d_out = x.d_out; c->d_committed = x.d_committed;
-  c->h_pods = x.h_pods; c->h_seq = x.h_seq; c->h_out = x.h_out; c->h_committed = x.h_committed;
-  for (int i = 0; i < 6; ++i) c->ev[i] = x.ev[i];
-  c->d_lst = x.d_lst; c->d_hist = x.d_hist;
-  c->d_tb = x.d_tb;
-  c->cur_slot = s;
 }
 
 constexpr int GS_REDO = 1;   // internal: re-run the batch (its score rows were overwritten by a speculative pass)
@@ -1286,121 +1276,123 @@ bool direct_batch(const gs_ctx* c, int b, bool speculative) {
   return !speculative && b <= SHORT_BATCH && lvl_ranks(c) == 1;
 }
 
-bool cand_overlapped(const gs_ctx* c) {
-  return c->cand_overlap && lvl_ranks(c) == 1 && !c->window_k && c->d_lst;
+bool cand_overlapped(const gs_ctx* c, const Slot& s) {
+  return c->cand_overlap && lvl_ranks(c) == 1 && !c->window_k && s.d_lst;
 }
 
-CommitArgs commit_args(gs_ctx* c, int b) {
+CommitArgs commit_args(gs_ctx* c, const Slot& s, int b) {
   CommitArgs a{};
   a.m = c->mv;
-  a.pods = c->d_pods;
-  a.seq = c->d_seq;
+  a.pods = s.d_pods.get();
+  a.seq = s.d_seq;
   a.npods = b;
   a.nranks = lvl_ranks(c);
   a.shard_size = (c->N + a.nranks - 1) / a.nranks;
   // several ranks: the speculative commit reads the merged levels, the pipelined / lockstep kernels every rank block
-  a.xbase = a.nranks == 1 ? (cand_overlapped(c) ? c->d_lst : c->d_xchg_send)
-                            : commit_spec_selected(c->window_k) ? c->d_xmerged : c->d_xchg_recv;
+  a.xbase = a.nranks == 1 ? (cand_overlapped(c, s) ? s.d_lst.get() : c->d_xchg_send.get())
+                            : commit_spec_selected(c->window_k) ? c->d_xmerged.get() : c->d_xchg_recv.get();
   a.xblock = c->xchg_bytes;
   a.bmax = c->B;
   a.pf = c->pf;
   a.seed = c->cfg.seed;
   a.forced_node = -1;
-  a.out = c->d_out;
-  a.committed = c->d_committed;
-  a.stamps = c->d_stamps;
-  a.topos = c->d_topos;
-  a.aff = c->d_aff;
+  a.out = s.d_out;
+  a.committed = s.d_committed.get();
+  a.stamps = c->d_stamps.get();
+  a.topos = c->d_topos.get();
+  a.aff = s.d_aff.get();
   a.ld = c->ld;
   a.own0 = c->n0;
   a.own1 = c->n1;
-  a.S = a.nranks == 1 ? c->d_S : nullptr;
-  a.S_own = c->d_S;
+  a.S = a.nranks == 1 ? s.d_S.get() : nullptr;
+  a.S_own = s.d_S.get();
   a.window_k = c->window_k;
   a.start = c->next_start;
   a.nnodes = c->N;
-  a.tb = c->d_tb;
-  a.landed = c->slot[c->cur_slot].d_landed;
-  // (score rows: the batch slot's verdict of unpack_scores_kernel; levels: merge_levels_kernel's)
-  a.xerr = c->sgather ? c->d_xerr + (XERR_BYTES / 4) * c->cur_slot : c->nranks > 1 ? c->d_xerr : nullptr;
+  a.tb = s.d_tb;
+  a.landed = s.d_landed.get();
+  a.xerr = s.d_xerr;
   return a;
 }
 
-// Enqueue one device pass over pods [0, b) of the bound slot's staged batch, and its read-back; no host wait.
-// The eval pass runs on st_ev, the rest on st. prev != nullptr: a speculative pass behind the batch that wrote `prev`
-// (its placements prev_out, prev_b pods): its eval pass runs beside that batch's commit, on the mirror as it was
-// before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel); its commit
-// kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
-int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev_out = nullptr, int prev_b = 0) {
-  const bool ovl = cand_overlapped(c);
-  uint8_t* lblk = ovl ? c->d_lst : c->d_xchg_send;
+// Enqueue one device pass over pods [0, b) of slot s's staged batch, and its read-back; no host wait.
+// The eval pass runs on st_ev, the rest on st. before != nullptr: a speculative pass behind slot `before`'s batch of
+// prev_b pods (prev: its committed words, prev_out: its placements): its eval pass runs beside that batch's commit, on
+// the mirror as it was before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel);
+// its commit kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
+int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0) {
+  const int32_t* prev = before ? before->d_committed.get() : nullptr;
+  const PlacementDev* prev_out = before ? before->d_out : nullptr;
+  const hipStream_t st = c->st.get(), st_ev = c->st_ev.get();
+  PodVec *const d_pods = s.d_pods.get(), *const h_pods = s.h_pods.get();
+  int16_t* const d_S = s.d_S.get();
+  uint8_t* const d_aff = s.d_aff.get();
+  const bool ovl = cand_overlapped(c, s);
+  uint8_t* lblk = ovl ? s.d_lst.get() : c->d_xchg_send.get();
   uint32_t* d_lists = reinterpret_cast<uint32_t*>(lblk);
   LevelHdr* d_hdrs = reinterpret_cast<LevelHdr*>(lblk + lists_bytes(c->B, c->lstride));
   LevelExt* d_ext = reinterpret_cast<LevelExt*>(lblk + lists_bytes(c->B, c->lstride) + (size_t)c->B * sizeof(LevelHdr));
   int prod_cols = 0;
-  for (int i = 0; i < b; ++i) prod_cols |= (c->h_pods[i].flags & PF_PROD_SCORE) ? 1 : 0;
+  for (int i = 0; i < b; ++i) prod_cols |= (h_pods[i].flags & PF_PROD_SCORE) ? 1 : 0;
   uint32_t len = c->n1 - c->n0;
   if (c->numa_on && (c->numa_idx_stale || c->numa_idx_lo != c->e0 || c->numa_idx_hi != c->e1)) {
     std::vector<uint32_t> idx;   // the policy nodes this rank evaluates
     for (uint32_t n = c->e0; n < c->e1; ++n)
       if (c->numa[n].cfg.numa_topology_policy != GS_NUMA_POLICY_NONE) idx.push_back(n);
     if (c->d_numa_idx) {
-      HIP_TRY(c, host_wait_stream(c->st));
-      HIP_TRY(c, host_wait_stream(c->st_ev));
-      (void)hipFree(c->d_numa_idx);
-      c->d_numa_idx = nullptr;
+      HIP_TRY(c, host_wait_stream(st));
+      HIP_TRY(c, host_wait_stream(st_ev));
+      c->d_numa_idx.reset();
     }
     c->numa_n = (uint32_t)idx.size();
     if (c->numa_n) {
-      HIP_TRY(c, hipMalloc(&c->d_numa_idx, 4 * idx.size()));
-      HIP_TRY(c, hipMemcpy(c->d_numa_idx, idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_numa_idx.alloc(4 * idx.size()));
+      HIP_TRY(c, hipMemcpy(c->d_numa_idx.get(), idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
     }
     if (c->numa_n > c->slab_cap) {   // columns of numa_n entries (rounded), the mirror's numbering
-      HIP_TRY(c, host_wait_stream(c->st_ev));
-      if (c->slab_mv.i64) (void)hipFree(c->slab_mv.i64);
-      if (c->slab_mv.i32) (void)hipFree(c->slab_mv.i32);
+      HIP_TRY(c, host_wait_stream(st_ev));
       c->slab_mv = MirrorView{nullptr, nullptr, 0};
+      c->slab_i64.reset();
+      c->slab_i32.reset();
       c->slab_cap = (c->numa_n + 1023) & ~1023u;
-      HIP_TRY(c, hipMalloc(&c->slab_mv.i64, (size_t)NUM_I64_COLS * c->slab_cap * 8));
-      HIP_TRY(c, hipMalloc(&c->slab_mv.i32, (size_t)NUM_I32_COLS * c->slab_cap * 4));
-      c->slab_mv.npad = c->slab_cap;
+      HIP_TRY(c, c->slab_i64.alloc((size_t)NUM_I64_COLS * c->slab_cap * 8));
+      HIP_TRY(c, c->slab_i32.alloc((size_t)NUM_I32_COLS * c->slab_cap * 4));
+      c->slab_mv = MirrorView{c->slab_i64.get(), c->slab_i32.get(), c->slab_cap};
     }
     c->numa_idx_stale = false;
     c->numa_idx_lo = c->e0;
     c->numa_idx_hi = c->e1;
   }
-  const gs_ctx::Slot& sl = c->slot[c->cur_slot];
   // a short batch with no pass beside it: upload, eval and levels in order on st (no queue hops)
   const bool direct = direct_batch(c, b, prev != nullptr);
-  hipStream_t se = direct ? c->st : c->st_ev;
+  hipStream_t se = direct ? st : st_ev;
   // full batches: readback on its own stream, so that the speculative next batch's patch / cand start right after the
   // commit (the slot's buffers are rewritten only after finish_batch has waited for ev[5]). Short batches (the host
   // waits on each one) keep it in order on st: the extra queue hop costs more than it hides there.
-  hipStream_t rb = b >= SHORT_BATCH ? c->st_rb : c->st;
+  hipStream_t rb = b >= SHORT_BATCH ? c->st_rb.get() : st;
   // A direct batch read back on st records no timing events: three HIP calls less per short plain run (C5 at 100k nodes,
   // medians of 7 alternations: 23.6k against 21.8k pods/s); its eval and levels intervals are not counted in the stats,
   // the commit's comes from the kernel. (st_rb waits on ev[4]: a batch read back there is always timed.)
-  const bool untimed = direct && rb == c->st;
-  c->slot[c->cur_slot].untimed = untimed;
-  if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[0], se));
+  const bool untimed = direct && rb == st;
+  s.untimed = untimed;
+  if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[0].get(), se));
   if (c->sgather) {
     // several ranks, score rows: this rank's shard into its block of the all-gather (rows of sx_pld entries), then the
     // R blocks into the full-width rows S / aff: every rank continues with the one-shard pipeline over all nodes
     const uint32_t pld = c->sx_pld;
-    uint8_t* blk = c->d_sx_send + c->sx_bytes * c->cur_slot;
-    uint8_t* rcv = c->d_sx_recv + c->sx_bytes * c->nranks * c->cur_slot;
-    HIP_TRY(c, launch_eval(c->mv, c->d_pods, b, c->pf, c->e0, c->e1, reinterpret_cast<int16_t*>(blk), pld, prod_cols,
-                           c->d_numa_idx, c->numa_n, blk + (size_t)b * pld * 2, se, c->st2, c->ev_fork, c->ev_join,
-                           c->slab_mv.i64 ? &c->slab_mv : nullptr));
-    if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[1], se));
+    uint8_t *blk = s.d_sx_send, *rcv = s.d_sx_recv;
+    HIP_TRY(c, launch_eval(c->mv, d_pods, b, c->pf, c->e0, c->e1, reinterpret_cast<int16_t*>(blk), pld, prod_cols,
+                           c->d_numa_idx.get(), c->numa_n, blk + (size_t)b * pld * 2, se, c->st2.get(),
+                           c->ev_fork.get(), c->ev_join.get(), c->slab_mv.i64 ? &c->slab_mv : nullptr));
+    if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[1].get(), se));
     const size_t bytes = ((size_t)b * pld * 3 + sizeof(XTag) + 255) / 256 * 256;
     if (int rc = exchange(c, XSITE_SCORES, blk, rcv, bytes, nullptr, se)) return rc;
-    HIP_TRY(c, launch_unpack_scores(rcv, bytes, c->nranks, b, c->sx_per, pld, c->N, c->d_S, c->d_aff, c->ld,
-                                    c->d_xerr + (XERR_BYTES / 4) * c->cur_slot, se));
+    HIP_TRY(c, launch_unpack_scores(rcv, bytes, c->nranks, b, c->sx_per, pld, c->N, d_S, d_aff, c->ld, s.d_xerr, se));
   } else {
-    HIP_TRY(c, launch_eval(c->mv, c->d_pods, b, c->pf, c->n0, c->n1, c->d_S, c->ld, prod_cols, c->d_numa_idx, c->numa_n,
-                           c->d_aff, se, c->st2, c->ev_fork, c->ev_join, c->slab_mv.i64 ? &c->slab_mv : nullptr));
-    if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[1], se));
+    HIP_TRY(c, launch_eval(c->mv, d_pods, b, c->pf, c->n0, c->n1, d_S, c->ld, prod_cols, c->d_numa_idx.get(), c->numa_n,
+                           d_aff, se, c->st2.get(), c->ev_fork.get(), c->ev_join.get(),
+                           c->slab_mv.i64 ? &c->slab_mv : nullptr));
+    if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[1].get(), se));
   }
   const bool fix = ovl && prev && prev_b > 0;
   int32_t tb_ready = 0;
@@ -1409,93 +1401,93 @@ int launch_batch(gs_ctx* c, int b, const int32_t* prev, const PlacementDev* prev
     // prev_b nodes, histogram kept), fixed up on st below once it committed
     CandPatch cp{};
     cp.extra = fix ? prev_b : 0;
-    cp.hist = fix ? c->d_hist : nullptr;
+    cp.hist = fix ? s.d_hist.get() : nullptr;
     // the batch's tie-break records too (off the commit's prologue); a short batch split over cs_* kernels leaves them
     // to the commit
-    cp.tb = c->d_tb;
-    cp.seq = c->d_seq;
+    cp.tb = s.d_tb;
+    cp.seq = s.d_seq;
     cp.seed = c->cfg.seed;
-    HIP_TRY(c, launch_cand(c->d_S, c->ld, len, c->n0, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, se, &cp,
-                           c->d_cscratch, &tb_ready));
+    HIP_TRY(c, launch_cand(d_S, c->ld, len, c->n0, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, se, &cp,
+                           c->d_cscratch.get(), &tb_ready));
   }
   if (!direct) {
-    HIP_TRY(c, hipEventRecord(sl.ev_evdone, c->st_ev));
-    HIP_TRY(c, hipStreamWaitEvent(c->st, sl.ev_evdone, 0));
+    HIP_TRY(c, hipEventRecord(s.ev_evdone.get(), st_ev));
+    HIP_TRY(c, hipStreamWaitEvent(st, s.ev_evdone.get(), 0));
   } else {   // the next speculative pass on st_ev (gather into the shared slab, eval) after this one
-    HIP_TRY(c, hipEventRecord(sl.ev_evdone, c->st));
-    HIP_TRY(c, hipStreamWaitEvent(c->st_ev, sl.ev_evdone, 0));
+    HIP_TRY(c, hipEventRecord(s.ev_evdone.get(), st));
+    HIP_TRY(c, hipStreamWaitEvent(st_ev, s.ev_evdone.get(), 0));
   }
   if (fix) {
-    CandPatch cp{c->mv, c->d_pods, c->pf, c->n0, c->n1, prod_cols, 0, c->d_aff, prev_out, prev};
+    CandPatch cp{c->mv, d_pods, c->pf, c->n0, c->n1, prod_cols, 0, d_aff, prev_out, prev};
     cp.extra = prev_b;
-    cp.hist = c->d_hist;
-    cp.landed = c->slot[1 - c->cur_slot].d_landed;   // (a speculative pass: the previous batch is the other slot's)
-    HIP_TRY(c, launch_fix_levels(c->d_S, c->ld, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, cp, c->st));
+    cp.hist = s.d_hist.get();
+    cp.landed = before->d_landed.get();   // (the slab the previous batch's commit leaves)
+    HIP_TRY(c, launch_fix_levels(d_S, c->ld, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, cp, st));
   }
   // the rows the previous batch landed on, re-evaluated on their committed state: inside cand_kernel (block k patches
   // pod k's row before its histogram; one launch less on the commit chain), or by patch_kernel under node sampling
   // (no candidate levels)
   const bool fused = prev && prev_b > 0 && !c->window_k;
   if (!ovl && prev && !fused)
-    HIP_TRY(c, launch_patch(c->mv, c->d_pods, b, c->pf, c->n0, c->n1, c->d_S, c->ld, prod_cols, c->d_aff, prev_out,
-                            prev, prev_b, c->st));
+    HIP_TRY(c, launch_patch(c->mv, d_pods, b, c->pf, c->n0, c->n1, d_S, c->ld, prod_cols, d_aff, prev_out, prev, prev_b,
+                            st));
   if (!c->window_k && !ovl) {   // node sampling selects over the rotation window, not the candidate levels
-    CandPatch cp{c->mv, c->d_pods, c->pf, c->n0, c->n1, prod_cols, 1, c->d_aff, prev_out, prev};
-    HIP_TRY(c, launch_cand(c->d_S, c->ld, len, c->n0, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, c->st,
-                           fused ? &cp : nullptr, c->d_cscratch));
+    CandPatch cp{c->mv, d_pods, c->pf, c->n0, c->n1, prod_cols, 1, d_aff, prev_out, prev};
+    HIP_TRY(c, launch_cand(d_S, c->ld, len, c->n0, b, c->max_score, c->lstride, d_lists, d_hdrs, d_ext, st,
+                           fused ? &cp : nullptr, c->d_cscratch.get()));
   }
   // no timing markers between the levels and the commit kernel (each one held the commit's dispatch ~13 us): the
   // commit's duration comes from the kernel itself (committed[4]), the levels' interval is the rest up to ev[4]
   if (lvl_ranks(c) > 1) {
-    int rc = exchange(c, XSITE_LEVELS, c->d_xchg_send, c->d_xchg_recv, c->xchg_bytes);
+    int rc = exchange(c, XSITE_LEVELS, c->d_xchg_send.get(), c->d_xchg_recv.get(), c->xchg_bytes);
     if (rc) return rc;
     if (!commit_spec_selected(c->window_k)) return fail(c, GS_EUNSUPPORTED, "several ranks need the speculative commit");
-    HIP_TRY(c, launch_merge_levels(c->d_xchg_recv, c->xchg_bytes, c->nranks, b, c->B, c->lstride, c->d_xmerged,
-                                   c->d_xerr, c->st));
+    HIP_TRY(c, launch_merge_levels(c->d_xchg_recv.get(), c->xchg_bytes, c->nranks, b, c->B, c->lstride,
+                                   c->d_xmerged.get(), s.d_xerr, st));
   }
-  CommitArgs a = commit_args(c, b);
+  CommitArgs a = commit_args(c, s, b);
   a.prev = prev;
   a.tb_ready = tb_ready;
   ++c->xbatch;
-  HIP_TRY(c, launch_commit(a, c->st));
-  if (!untimed) HIP_TRY(c, hipEventRecord(c->ev[4], c->st));
-  if (rb != c->st) HIP_TRY(c, hipStreamWaitEvent(rb, c->ev[4], 0));
+  HIP_TRY(c, launch_commit(a, st));
+  if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
+  if (rb != st) HIP_TRY(c, hipStreamWaitEvent(rb, s.ev[4].get(), 0));
   // Two copies, not one over the adjacent committed words and placements: with one merged copy, 4 processes sharing the
   // GPU (the C4 rehearsal) stalled for 10-100 s at a time, every rank's commit and next eval pass pending;
   // for a direct batch the merged form measured within noise
-  HIP_TRY(c, hipMemcpyAsync(c->h_committed, c->d_committed, COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
-  HIP_TRY(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
-  HIP_TRY(c, hipEventRecord(c->ev[5], rb));
+  HIP_TRY(c, hipMemcpyAsync(s.h_committed.get(), s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
+  HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
+  HIP_TRY(c, hipEventRecord(s.ev[5].get(), rb));
   return GS_OK;
 }
 
-// Wait for the bound slot's batch; when it committed nothing, resolve its pod 0 by the exact full-row path
+// Wait for slot s's batch; when it committed nothing, resolve its pod 0 by the exact full-row path
 // (several shards). clobbered: a speculative pass has overwritten the score rows and lists since -> GS_REDO.
-int finish_batch(gs_ctx* c, int b, bool clobbered, int* committed_out) {
+int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) {
   uint32_t len = c->n1 - c->n0;
+  const hipStream_t st = c->st.get();
+  int32_t* const h_committed = s.h_committed.get();
   {
     Where w_(c, "finish_batch: the batch's readback event");
-    HIP_TRY(c, host_wait_event(c->ev[5]));
+    HIP_TRY(c, host_wait_event(s.ev[5].get()));
   }
   flush_exchange_times(c);
-  const bool untimed = c->slot[c->cur_slot].untimed;
-  if (!untimed) c->stats.eval_ms += ev_ms(c->ev[0], c->ev[1]);
+  if (!s.untimed) c->stats.eval_ms += ev_ms(s.ev[0].get(), s.ev[1].get());
   {   // commit kernel: its own duration (s_memrealtime, 100 MHz) in committed[4]; levels: the rest from the eval's end
-    const double cm = (double)(uint32_t)c->h_committed[4] * 1e-5;
+    const double cm = (double)(uint32_t)h_committed[4] * 1e-5;
     c->stats.commit_ms += cm;
-    if (!untimed) c->stats.cand_ms += std::max(0.0, ev_ms(c->ev[1], c->ev[4]) - cm);
+    if (!s.untimed) c->stats.cand_ms += std::max(0.0, ev_ms(s.ev[1].get(), s.ev[4].get()) - cm);
   }
   c->stats.eval_launches += 1;
   c->stats.eval_pairs += (uint64_t)b * (c->e1 - c->e0);
   c->stats.batches += 1;
-  int committed = c->h_committed[0];
+  int committed = h_committed[0];
   if (committed < 0) return fail(c, GS_ESTATE, "commit pass of a batch was voided unexpectedly");
-  if (c->h_committed[3] == COMMIT_ERR_XTAG) {   // the level exchange paired different exchanges of the ranks
+  if (h_committed[3] == COMMIT_ERR_XTAG) {   // the level exchange paired different exchanges of the ranks
     // the first mismatching exchange's tags, as merge_levels_kernel kept them
     std::vector<uint8_t> xe(XERR_BYTES);
-    HIP_TRY(c, host_wait_stream(c->st));
-    HIP_TRY(c, hipMemcpy(xe.data(), c->d_xerr + (c->sgather ? (XERR_BYTES / 4) * c->cur_slot : 0), xe.size(),
-                         hipMemcpyDeviceToHost));
+    HIP_TRY(c, host_wait_stream(st));
+    HIP_TRY(c, hipMemcpy(xe.data(), s.d_xerr, xe.size(), hipMemcpyDeviceToHost));
     const uint8_t* tags = xe.data() + 4 * XERR_TAGS;
     XTag mine;
     std::memcpy(&mine, tags + (size_t)c->rank * sizeof(XTag), sizeof mine);
@@ -1503,27 +1495,27 @@ int finish_batch(gs_ctx* c, int b, bool clobbered, int* committed_out) {
     return fail(c, GS_ECOMM, "exchange sequence diverged at a %s exchange (device check)",
                 c->sgather ? "score-row" : "level");
   }
-  if (c->h_committed[3])
-    return fail(c, GS_EDEVICE, "commit kernel: a pipeline wait expired (internal error, site %d)", c->h_committed[3]);
+  if (h_committed[3])
+    return fail(c, GS_EDEVICE, "commit kernel: a pipeline wait expired (internal error, site %d)", h_committed[3]);
   if (c->window_k) {
     if (committed == 0) return fail(c, GS_ESTATE, "node-sampling commit made no progress");
-    c->next_start = (uint32_t)c->h_committed[2];
+    c->next_start = (uint32_t)h_committed[2];
     c->stats.next_start_node_index = c->next_start;
   }
   if (committed == 0 && clobbered) return GS_REDO;
   if (committed == 0) {
-    CommitArgs a = commit_args(c, b);
+    CommitArgs a = commit_args(c, s, b);
     // exact full-row path for pod 0: (max, ties, feasible) of every shard's row, global selection
-    HIP_TRY(c, launch_row_stats(c->d_S, len, c->d_rowstat, c->st));
+    HIP_TRY(c, launch_row_stats(s.d_S.get(), len, c->d_rowstat.get(), st));
     const int lr = lvl_ranks(c);
     std::vector<RowStat> rs(lr);
     if (lr > 1) {
-      int rc = exchange_small(c, XSITE_ROWSTAT, c->d_rowstat, sizeof(RowStat), rs.data());
+      int rc = exchange_small(c, XSITE_ROWSTAT, c->d_rowstat.get(), sizeof(RowStat), rs.data());
       if (rc) return rc;
     } else {
-      HIP_TRY(c, hipMemcpyAsync(rs.data(), c->d_rowstat, sizeof(RowStat), hipMemcpyDeviceToHost, c->st));
+      HIP_TRY(c, hipMemcpyAsync(rs.data(), c->d_rowstat.get(), sizeof(RowStat), hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(c, host_wait_stream(c->st));
+    HIP_TRY(c, host_wait_stream(st));
     int M = -1;
     int64_t T = 0, F = 0;
     for (const auto& r : rs) {
@@ -1532,11 +1524,11 @@ int finish_batch(gs_ctx* c, int b, bool clobbered, int* committed_out) {
       else if (r.max_score == M && M >= 0) T += r.ties;
     }
     if (M < 0) {
-      c->h_out[0] = PlacementDev{-1, (uint32_t)F, 0, 0, GS_PLACED_SLOWPATH, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      s.h_out[0] = PlacementDev{-1, (uint32_t)F, 0, 0, GS_PLACED_SLOWPATH, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
       *committed_out = 1;
       return GS_OK;
     }
-    int64_t jstar = host_tiebreak_position(c->cfg.seed, c->h_seq[0], T);
+    int64_t jstar = host_tiebreak_position(c->cfg.seed, s.h_seq[0], T);
     int owner = -1;
     int64_t before = 0;
     for (int r = 0; r < lr; ++r) {
@@ -1546,43 +1538,43 @@ int finish_batch(gs_ctx* c, int b, bool clobbered, int* committed_out) {
     }
     int32_t winner = -1;
     if (owner == (lr > 1 ? c->rank : 0)) {
-      HIP_TRY(c, launch_row_select(c->d_S, len, M, jstar - before, c->n0, c->d_sel, c->st));
+      HIP_TRY(c, launch_row_select(s.d_S.get(), len, M, jstar - before, c->n0, c->d_sel.get(), st));
     } else {
-      HIP_TRY(c, hipMemsetAsync(c->d_sel, 0xff, 4, c->st));
+      HIP_TRY(c, hipMemsetAsync(c->d_sel.get(), 0xff, 4, st));
     }
     if (lr > 1) {
       std::vector<int32_t> w(lr);
-      int rc = exchange_small(c, XSITE_SELECT, c->d_sel, 4, w.data());
+      int rc = exchange_small(c, XSITE_SELECT, c->d_sel.get(), 4, w.data());
       if (rc) return rc;
       winner = w[owner];
     } else {
-      HIP_TRY(c, hipMemcpyAsync(&winner, c->d_sel, 4, hipMemcpyDeviceToHost, c->st));
-      HIP_TRY(c, host_wait_stream(c->st));
+      HIP_TRY(c, hipMemcpyAsync(&winner, c->d_sel.get(), 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, host_wait_stream(st));
     }
     if (winner < 0) return fail(c, GS_ESTATE, "exact path could not locate tie %lld", (long long)jstar);
     a.forced_node = winner;
     a.forced_score = M;
     a.forced_ties = T;
     a.forced_feasible = (int32_t)F;
-    HIP_TRY(c, hipEventRecord(c->ev[3], c->st));
-    HIP_TRY(c, launch_commit(a, c->st));
-    HIP_TRY(c, hipEventRecord(c->ev[4], c->st));
-    HIP_TRY(c, hipMemcpyAsync(c->h_committed, c->d_committed, COMMITTED_BYTES, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(c, host_wait_stream(c->st));
-    c->stats.commit_ms += ev_ms(c->ev[3], c->ev[4]);
-    committed = c->h_committed[0];
+    HIP_TRY(c, hipEventRecord(s.ev[3].get(), st));
+    HIP_TRY(c, launch_commit(a, st));
+    HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
+    HIP_TRY(c, hipMemcpyAsync(h_committed, s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, host_wait_stream(st));
+    c->stats.commit_ms += ev_ms(s.ev[3].get(), s.ev[4].get());
+    committed = h_committed[0];
     if (committed < 1) return fail(c, GS_ESTATE, "forced commit made no progress");
-    HIP_TRY(c, hipMemcpyAsync(c->h_out, c->d_out, sizeof(PlacementDev) * committed, hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(c, host_wait_stream(c->st));
+    HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * committed, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, host_wait_stream(st));
   }
   flush_exchange_times(c);
   if (committed < b) {
     c->stats.cuts += 1;
     static const bool dbg = env_on("GS_DEBUG_CUTS");
     if (dbg) {
-      const PlacementDev& x = c->h_out[committed];
+      const PlacementDev& x = s.h_out[committed];
       fprintf(stderr, "gpuscore: batch of %d ended after %d pods (code %#x) [%d run %u M %lld Mc %lld Md %lld T %u Tc %d new %u old %u jp %lld nd %lld pend %lld]\n",
-              b, committed, c->h_committed[2], x.node, x.feasible, (long long)(x.score & 0xfffff),
+              b, committed, h_committed[2], x.node, x.feasible, (long long)(x.score & 0xfffff),
               (long long)((x.score >> 20) & 0xfffff), (long long)(x.score >> 40), x.ties, (int)x.flags, x.zkeys, x.pad,
               (long long)x.zcpu[0], (long long)x.zcpu[1], (long long)x.zcpu[2]);
       fprintf(stderr, "   old slot %lld node %llu hash %lld S %d dso %d\n", (long long)x.cpuset[0],
@@ -1647,18 +1639,18 @@ DevNode dev_image(const gs_ctx* c, uint32_t i) {
 
 int ext_alloc(gs_ctx* c) {
   if (c->d_dev) return GS_OK;
-  HIP_TRY(c, hipMalloc(&c->d_dev, sizeof(DevNode) * std::max<uint32_t>(1, c->N)));
+  HIP_TRY(c, c->d_dev.alloc(sizeof(DevNode) * std::max<uint32_t>(1, c->N)));
   std::vector<DevNode> img(c->N);
   for (uint32_t i = 0; i < c->N; ++i) img[i] = dev_image(c, i);
-  HIP_TRY(c, hipMemcpy(c->d_dev, img.data(), sizeof(DevNode) * c->N, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->d_dev.get(), img.data(), sizeof(DevNode) * c->N, hipMemcpyHostToDevice));
   c->dev_dirty_list.clear();
   std::fill(c->dev_dirty.begin(), c->dev_dirty.end(), 0);
-  HIP_TRY(c, hipMalloc(&c->d_xtot, 4 * (size_t)c->ld));
-  HIP_TRY(c, hipMalloc(&c->d_xT, 4 * ext_select_scratch_words(c->ld)));
-  HIP_TRY(c, hipMalloc(&c->d_xds, 2 * (size_t)c->ld));
-  HIP_TRY(c, hipMalloc(&c->d_xrs, 2 * (size_t)c->ld));
-  HIP_TRY(c, hipMalloc(&c->d_xout, sizeof(ExtOut)));
-  HIP_TRY(c, hipHostMalloc(&c->h_xout, sizeof(ExtOut), hipHostMallocDefault));   // written by ext_finish_kernel
+  HIP_TRY(c, c->d_xtot.alloc(4 * (size_t)c->ld));
+  HIP_TRY(c, c->d_xT.alloc(4 * ext_select_scratch_words(c->ld)));
+  HIP_TRY(c, c->d_xds.alloc(2 * (size_t)c->ld));
+  HIP_TRY(c, c->d_xrs.alloc(2 * (size_t)c->ld));
+  HIP_TRY(c, c->d_xout.alloc(sizeof(ExtOut)));
+  HIP_TRY(c, c->h_xout.alloc(sizeof(ExtOut)));   // written by ext_finish_kernel
   return GS_OK;
 }
 
@@ -1673,20 +1665,16 @@ int ext_stage_reserve(gs_ctx* c, uint32_t nrec, uint32_t nres) {
   c->xin_off_rec = off_pv + al(sizeof(PodVec));
   c->xin_off_res = c->xin_off_rec + al(sizeof(ExtRec) * c->xrec_cap);
   c->xin_bytes = c->xin_off_res + sizeof(ExtRes) * c->xres_cap;
-  HIP_TRY(c, host_wait_stream(c->st));
-  if (c->h_xin) (void)hipHostFree(c->h_xin);
-  if (c->d_xin) (void)hipFree(c->d_xin);
-  if (c->d_xnom) (void)hipFree(c->d_xnom);
-  if (c->h_xnom) (void)hipHostFree(c->h_xnom);
-  HIP_TRY(c, hipHostMalloc(&c->h_xin, c->xin_bytes, hipHostMallocDefault));
-  HIP_TRY(c, hipMalloc(&c->d_xin, c->xin_bytes));
-  HIP_TRY(c, hipMalloc(&c->d_xnom, 4 * c->xrec_cap));
-  HIP_TRY(c, hipHostMalloc(&c->h_xnom, 4 * c->xrec_cap, hipHostMallocDefault));   // written by ext_finish_kernel
-  c->h_xpod = reinterpret_cast<ExtPod*>(c->h_xin);
-  c->d_xpod = reinterpret_cast<ExtPod*>(c->d_xin);
-  c->d_xpv = reinterpret_cast<PodVec*>(c->d_xin + off_pv);
-  c->d_xrec = reinterpret_cast<ExtRec*>(c->d_xin + c->xin_off_rec);
-  c->d_xres = reinterpret_cast<ExtRes*>(c->d_xin + c->xin_off_res);
+  HIP_TRY(c, host_wait_stream(c->st.get()));
+  HIP_TRY(c, c->h_xin.alloc(c->xin_bytes));   // (alloc() frees the old block: the wait above covers the four)
+  HIP_TRY(c, c->d_xin.alloc(c->xin_bytes));
+  HIP_TRY(c, c->d_xnom.alloc(4 * c->xrec_cap));
+  HIP_TRY(c, c->h_xnom.alloc(4 * c->xrec_cap));   // written by ext_finish_kernel
+  c->h_xpod = reinterpret_cast<ExtPod*>(c->h_xin.get());
+  c->d_xpod = reinterpret_cast<ExtPod*>(c->d_xin.get());
+  c->d_xpv = reinterpret_cast<PodVec*>(c->d_xin.get() + off_pv);
+  c->d_xrec = reinterpret_cast<ExtRec*>(c->d_xin.get() + c->xin_off_rec);
+  c->d_xres = reinterpret_cast<ExtRes*>(c->d_xin.get() + c->xin_off_res);
   return GS_OK;
 }
 
@@ -1695,22 +1683,23 @@ int ext_flush_devices(gs_ctx* c) {
   if (c->dev_dirty_list.empty()) return GS_OK;
   if (!c->d_dev) return ext_alloc(c);
   if (!c->h_dev_stage) {   // n images, then their node indices: one copy
-    HIP_TRY(c, hipHostMalloc(&c->h_dev_stage, (sizeof(DevNode) + 4) * EXT_DEV_STAGE, hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc(&c->d_dev_stage, (sizeof(DevNode) + 4) * EXT_DEV_STAGE));
+    HIP_TRY(c, c->h_dev_stage.alloc((sizeof(DevNode) + 4) * EXT_DEV_STAGE));
+    HIP_TRY(c, c->d_dev_stage.alloc((sizeof(DevNode) + 4) * EXT_DEV_STAGE));
   }
+  DevNode *const h_stage = c->h_dev_stage.get(), *const d_stage = c->d_dev_stage.get();
   for (size_t done = 0; done < c->dev_dirty_list.size();) {
     const uint32_t n = (uint32_t)std::min<size_t>(EXT_DEV_STAGE, c->dev_dirty_list.size() - done);
-    HIP_TRY(c, host_wait_stream(c->st));   // the previous scatter has consumed the staging buffers
-    uint32_t* h_idx = reinterpret_cast<uint32_t*>(c->h_dev_stage + n);
+    HIP_TRY(c, host_wait_stream(c->st.get()));   // the previous scatter has consumed the staging buffers
+    uint32_t* h_idx = reinterpret_cast<uint32_t*>(h_stage + n);
     for (uint32_t j = 0; j < n; ++j) {
       const uint32_t i = c->dev_dirty_list[done + j];
-      c->h_dev_stage[j] = dev_image(c, i);
+      h_stage[j] = dev_image(c, i);
       h_idx[j] = i;
       c->dev_dirty[i] = 0;
     }
-    HIP_TRY(c, hipMemcpyAsync(c->d_dev_stage, c->h_dev_stage, (sizeof(DevNode) + 4) * n, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(c, launch_scatter_devnodes(c->d_dev, reinterpret_cast<const uint32_t*>(c->d_dev_stage + n), c->d_dev_stage,
-                                       n, c->st));
+    HIP_TRY(c, hipMemcpyAsync(d_stage, h_stage, (sizeof(DevNode) + 4) * n, hipMemcpyHostToDevice, c->st.get()));
+    HIP_TRY(c, launch_scatter_devnodes(c->d_dev.get(), reinterpret_cast<const uint32_t*>(d_stage + n), d_stage, n,
+                                       c->st.get()));
     done += n;
   }
   c->dev_dirty_list.clear();
@@ -1938,57 +1927,63 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
   xp.seq = seq;
   // GPU names are scalar requests: the Fit filter's all-zero short cut no longer applies
   if (gpu_names_all || xres_all) v.flags &= ~PF_ALL_ZERO;
-  *reinterpret_cast<PodVec*>(c->h_xin + ((sizeof(ExtPod) + 15) & ~(size_t)15)) = v;
+  *reinterpret_cast<PodVec*>(c->h_xin.get() + ((sizeof(ExtPod) + 15) & ~(size_t)15)) = v;
   // the NUMA-policy work list over [n0, n1) for the eval pass and ext_numa_kernel (launch_batch's list is the shard's)
   if (c->numa_on && c->xnuma_stale) {
     std::vector<uint32_t> idx;
     for (uint32_t n = c->n0; n < c->n1; ++n)
       if (c->numa[n].cfg.numa_topology_policy != GS_NUMA_POLICY_NONE) idx.push_back(n);
-    HIP_TRY(c, host_wait_stream(c->st));
-    if (c->d_xnuma_idx) { (void)hipFree(c->d_xnuma_idx); c->d_xnuma_idx = nullptr; }
+    HIP_TRY(c, host_wait_stream(c->st.get()));
+    c->d_xnuma_idx.reset();
     c->xnuma_n = (uint32_t)idx.size();
     if (c->xnuma_n) {
-      HIP_TRY(c, hipMalloc(&c->d_xnuma_idx, 4 * idx.size()));
-      HIP_TRY(c, hipMemcpy(c->d_xnuma_idx, idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
+      HIP_TRY(c, c->d_xnuma_idx.alloc(4 * idx.size()));
+      HIP_TRY(c, hipMemcpy(c->d_xnuma_idx.get(), idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
     }
     c->xnuma_stale = false;
   }
   const int prod_cols = (v.flags & PF_PROD_SCORE) ? 1 : 0;
+  // no batch is in flight: the current slot's score rows, affinities and timing events serve this pod
+  Slot& sl = current_slot(c);
+  int16_t* const d_S = sl.d_S.get();
+  uint8_t* const d_aff = sl.d_aff.get();
+  const hipStream_t st = c->st.get();
+  DevNode* const d_dev = c->d_dev.get();
+  int32_t *const d_xtot = c->d_xtot.get(), *const d_xT = c->d_xT.get(), *const d_xnom = c->d_xnom.get();
+  int16_t *const d_xds = c->d_xds.get(), *const d_xrs = c->d_xrs.get();
   // inputs: one copy of the staged block (ExtPod, PodVec, the matched records and reservations)
   if (nrec) {
-    std::memcpy(c->h_xin + c->xin_off_rec, c->xrec.data(), sizeof(ExtRec) * nrec);
-    std::memcpy(c->h_xin + c->xin_off_res, c->xres.data(), sizeof(ExtRes) * c->xres.size());
+    std::memcpy(c->h_xin.get() + c->xin_off_rec, c->xrec.data(), sizeof(ExtRec) * nrec);
+    std::memcpy(c->h_xin.get() + c->xin_off_res, c->xres.data(), sizeof(ExtRes) * c->xres.size());
   }
   const size_t in_bytes = nrec ? c->xin_off_res + sizeof(ExtRes) * c->xres.size() : c->xin_off_rec;
   // no event markers inside the chain (each one holds the next dispatch for microseconds): the pass is timed on the
   // host, from the input copy's enqueue to the end of the stream synchronisation (GS_EXT_EVENTS=1: per-kernel events)
   static const bool ext_ev = env_on("GS_EXT_EVENTS");
   const auto ext_t0 = std::chrono::steady_clock::now();
-  HIP_TRY(c, hipMemcpyAsync(c->d_xin, c->h_xin, in_bytes, hipMemcpyHostToDevice, c->st));
-  if (ext_ev) HIP_TRY(c, hipEventRecord(c->ev[0], c->st));
-  HIP_TRY(c, launch_eval(c->mv, c->d_xpv, 1, c->pf, c->n0, c->n1, c->d_S, c->ld, prod_cols, c->d_xnuma_idx, c->xnuma_n,
-                         c->d_aff, c->st));
-  if (ext_ev) HIP_TRY(c, hipEventRecord(c->ev[1], c->st));
+  HIP_TRY(c, hipMemcpyAsync(c->d_xin.get(), c->h_xin.get(), in_bytes, hipMemcpyHostToDevice, st));
+  if (ext_ev) HIP_TRY(c, hipEventRecord(sl.ev[0].get(), st));
+  HIP_TRY(c, launch_eval(c->mv, c->d_xpv, 1, c->pf, c->n0, c->n1, d_S, c->ld, prod_cols, c->d_xnuma_idx.get(),
+                         c->xnuma_n, d_aff, st));
+  if (ext_ev) HIP_TRY(c, hipEventRecord(sl.ev[1].get(), st));
   // (ext_nodes_kernel also resets the select accumulators; ext_matched runs for pods with matched reservations only)
-  HIP_TRY(c, launch_ext_nodes(c->d_dev, c->d_S, c->n0, c->n1, c->d_xpod, c->d_xtot, c->d_xds, c->d_xrs, c->d_xT,
-                              c->st));
+  HIP_TRY(c, launch_ext_nodes(d_dev, d_S, c->n0, c->n1, c->d_xpod, d_xtot, d_xds, d_xrs, d_xT, st));
   // GPU pods on NUMA-policy nodes: DeviceShare is the topology manager's second hint provider
   if (gmask && c->numa_on && c->xnuma_n)
-    HIP_TRY(c, launch_ext_numa(c->mv, c->d_xpv, c->pf, prod_cols, c->d_dev, c->d_xpod, c->d_xnuma_idx, c->xnuma_n, c->n0,
-                               c->d_xtot, c->d_xds, c->d_aff, c->d_xT, c->n1 - c->n0, c->st));
+    HIP_TRY(c, launch_ext_numa(c->mv, c->d_xpv, c->pf, prod_cols, d_dev, c->d_xpod, c->d_xnuma_idx.get(), c->xnuma_n,
+                               c->n0, d_xtot, d_xds, d_aff, d_xT, c->n1 - c->n0, st));
   // the matched nodes last: their restored rows over the whole Filter chain (incl. the policy nodes' affinity)
   if (nrec)
-    HIP_TRY(c, launch_ext_matched(c->mv, c->d_xpv, c->pf, prod_cols, c->d_dev, c->d_xpod, c->d_xrec, c->d_xres, nrec,
-                                  c->d_xtot, c->d_xds, c->d_xrs, c->d_xnom, c->d_aff, c->n0, c->d_xT, c->n1 - c->n0,
-                                  c->st));
-  HIP_TRY(c, launch_ext_select(c->d_xtot, c->d_xds, c->d_xrs, c->d_xrec, c->n0, c->n1, c->d_xpod, c->cfg.seed, c->d_xT,
-                               c->d_xout, c->st));
+    HIP_TRY(c, launch_ext_matched(c->mv, c->d_xpv, c->pf, prod_cols, d_dev, c->d_xpod, c->d_xrec, c->d_xres, nrec,
+                                  d_xtot, d_xds, d_xrs, d_xnom, d_aff, c->n0, d_xT, c->n1 - c->n0, st));
+  HIP_TRY(c, launch_ext_select(d_xtot, d_xds, d_xrs, c->d_xrec, c->n0, c->n1, c->d_xpod, c->cfg.seed, d_xT,
+                               c->d_xout.get(), st));
   // outputs: the NodeNUMAResource Reserve of the selected node along its affinity, and the result and nominations
   // written straight into pinned host memory (no copy)
-  HIP_TRY(c, launch_ext_finish(c->mv, c->d_xpv, c->pf, prod_cols, c->d_aff, c->n0, c->numa_on ? 1 : 0, c->d_xout,
-                               c->d_xnom, nrec, c->h_xout, c->h_xnom, c->st));
-  if (ext_ev) HIP_TRY(c, hipEventRecord(c->ev[4], c->st));
-  HIP_TRY(c, host_wait_stream(c->st));
+  HIP_TRY(c, launch_ext_finish(c->mv, c->d_xpv, c->pf, prod_cols, d_aff, c->n0, c->numa_on ? 1 : 0, c->d_xout.get(),
+                               d_xnom, nrec, c->h_xout.get(), c->h_xnom.get(), st));
+  if (ext_ev) HIP_TRY(c, hipEventRecord(sl.ev[4].get(), st));
+  HIP_TRY(c, host_wait_stream(st));
   const auto hx3 = hx_clk::now();
   if (c->host_timing) {
     const auto us = [](hx_clk::duration d) { return std::chrono::duration<double, std::micro>(d).count(); };
@@ -1998,8 +1993,8 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     c->hx_pods += 1;
   }
   if (ext_ev) {
-    c->stats.eval_ms += ev_ms(c->ev[0], c->ev[1]);
-    c->stats.commit_ms += ev_ms(c->ev[1], c->ev[4]);
+    c->stats.eval_ms += ev_ms(sl.ev[0].get(), sl.ev[1].get());
+    c->stats.commit_ms += ev_ms(sl.ev[1].get(), sl.ev[4].get());
   } else {
     c->stats.commit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ext_t0).count();
   }
@@ -2007,7 +2002,8 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
   c->stats.eval_pairs += c->n1 - c->n0;
   c->stats.batches += 1;
   c->stats.pods += 1;
-  const ExtOut xo = *c->h_xout;
+  const ExtOut xo = *c->h_xout.get();
+  const int32_t* h_xnom = c->h_xnom.get();   // (the nominations ext_finish_kernel wrote)
   if (xo.err & 1u)
     return fail(c, GS_EUNSUPPORTED, "a GPU's NUMA node is not one of its node's NUMA zones (DeviceShare hints)");
   if (xo.err & 2u)
@@ -2046,7 +2042,7 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     if (it != c->xrec.end() && it->node == node) rec_i = (int)(it - c->xrec.begin());
   }
   if (rs_on && rec_i >= 0) {   // Reservation.Reserve -> reservationCache.assumePod (AddAssignedPod, reservation_info.go:379-388)
-    const int nom = c->h_xnom[rec_i];
+    const int nom = h_xnom[rec_i];
     if (nom >= 0) {
       gs_reservation& r = c->rsv.at(c->xres_uid[c->xrec[rec_i].first + nom]);
       for (int s = 0; s < 7; ++s)
@@ -2062,7 +2058,7 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     if (gpu_names_all >> n & 1u) { c->devs[node].requested[n] += e.gpu_requests[n]; dev_mark(c, node); }
   for (int x = 0; x < GS_MAX_XRES; ++x)         // ... and of the registered extended resources
     if (xres_all >> x & 1u) { c->devs[node].xres_requested[x] += e.xres_requests[x]; dev_mark(c, node); }
-  if (gmask || (rs_on && rec_i >= 0 && c->h_xnom[rec_i] >= 0) || gpu_names_all || xres_all)
+  if (gmask || (rs_on && rec_i >= 0 && h_xnom[rec_i] >= 0) || gpu_names_all || xres_all)
     c->ext_reserved.insert(pod.uid);   // gs_pods_forget cannot undo these Reserves
   apply_placement(c, pod, xo.node, true);
   if (c->host_timing)
@@ -2209,97 +2205,66 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   // host applying a batch's placements one batch late. CU-masked streams are blocking streams — they synchronise with
   // the null stream, which hipMemset / hipMemcpy / hipFree use — and a one-pod-batch test hung in gs_destroy's hipFree
   // with it; the commit measured no faster on a CU of its own. Removed)
-  if ((e = hipStreamCreateWithPriority(&c->st, hipStreamNonBlocking, prio_hi)) != hipSuccess) return bail("hipStreamCreate", e);
-  if ((e = hipStreamCreateWithPriority(&c->st2, hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
-  if ((e = hipStreamCreateWithPriority(&c->st_ev, hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
-  if ((e = hipStreamCreateWithFlags(&c->st_rb, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-  if ((e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-  if ((e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-  for (int i = 0; i < 6; ++i)
-    if ((e = hipEventCreate(&c->ev[i])) != hipSuccess) return bail("hipEventCreate", e);
+  if ((e = c->st.create(hipStreamNonBlocking, prio_hi)) != hipSuccess) return bail("hipStreamCreate", e);
+  if ((e = c->st2.create(hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
+  if ((e = c->st_ev.create(hipStreamNonBlocking, prio_lo)) != hipSuccess) return bail("hipStreamCreate", e);
+  if ((e = c->st_rb.create(hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
+  if ((e = c->ev_fork.create(hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+  if ((e = c->ev_join.create(hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
   size_t np = c->npad;
-  if ((e = hipMalloc(&c->d_i64, np * NUM_I64_COLS * 8)) != hipSuccess) return bail("hipMalloc mirror", e);
-  if ((e = hipMalloc(&c->d_i32, np * NUM_I32_COLS * 4)) != hipSuccess) return bail("hipMalloc mirror", e);
-  (void)hipMemset(c->d_i64, 0, np * NUM_I64_COLS * 8);
-  (void)hipMemset(c->d_i32, 0, np * NUM_I32_COLS * 4);
-  c->mv.i64 = c->d_i64;
-  c->mv.i32 = c->d_i32;
-  c->mv.npad = (uint32_t)np;
+  if ((e = c->mirror_i64.alloc(np * NUM_I64_COLS * 8)) != hipSuccess) return bail("hipMalloc mirror", e);
+  if ((e = c->mirror_i32.alloc(np * NUM_I32_COLS * 4)) != hipSuccess) return bail("hipMalloc mirror", e);
+  c->mv = MirrorView{c->mirror_i64.get(), c->mirror_i32.get(), (uint32_t)np};
+  (void)hipMemset(c->mv.i64, 0, np * NUM_I64_COLS * 8);
+  (void)hipMemset(c->mv.i32, 0, np * NUM_I32_COLS * 4);
   c->ld = c->npad;
-  // pods | seq and committed | out share one allocation each: one copy per batch each way
-  static_assert(sizeof(PodVec) % 8 == 0 && sizeof(PlacementDev) % 8 == 0, "staging layout");
-  if ((e = hipMalloc(&c->d_pods, (sizeof(PodVec) + 8) * c->B)) != hipSuccess) return bail("hipMalloc", e);
-  c->d_seq = reinterpret_cast<uint64_t*>(c->d_pods + c->B);
-  if ((e = hipMalloc(&c->d_S, (size_t)c->B * c->ld * 2)) != hipSuccess) return bail("hipMalloc S", e);
-  if ((e = hipMalloc(&c->d_aff, (size_t)c->B * c->ld)) != hipSuccess) return bail("hipMalloc aff", e);
   size_t xb = xchg_block_bytes(c->B, LCAP);
-  if ((e = hipMalloc(&c->d_xchg_send, xb)) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = c->d_xchg_send.alloc(xb)) != hipSuccess) return bail("hipMalloc", e);
   c->xchg_bytes = xb;
-  if ((e = hipMalloc(&c->d_committed, COMMITTED_BYTES + sizeof(PlacementDev) * c->B)) != hipSuccess) return bail("hipMalloc", e);
-  c->d_out = reinterpret_cast<PlacementDev*>(c->d_committed + COMMITTED_BYTES / 4);
-  if ((e = hipMalloc(&c->d_tb, sizeof(int32_t) * TB_N * c->B * 2)) != hipSuccess) return bail("hipMalloc", e);   // both slots'
-  if ((e = hipMalloc(&c->d_rowstat, sizeof(RowStat) * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
-  if ((e = hipMalloc(&c->d_sel, 4 * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = c->tb_all.alloc(sizeof(int32_t) * TB_N * c->B * 2)) != hipSuccess) return bail("hipMalloc", e);   // both slots'
+  if ((e = c->d_rowstat.alloc(sizeof(RowStat) * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = c->d_sel.alloc(4 * (1 + MAX_RANKS))) != hipSuccess) return bail("hipMalloc", e);
   c->stage_cap = std::min<uint32_t>(c->N, 65536);
   // staged rows then their node indices (flush_rows)
-  if ((e = hipMalloc(&c->d_stage_rows, (size_t)(8 * ROW_WORDS + 4) * c->stage_cap)) != hipSuccess) return bail("hipMalloc", e);
-  if ((e = hipHostMalloc(&c->h_stage_rows, (size_t)(8 * ROW_WORDS + 4) * c->stage_cap, hipHostMallocDefault)) != hipSuccess)
-    return bail("hipHostMalloc", e);
-  if ((e = hipHostMalloc(&c->h_pods, (sizeof(PodVec) + 8) * c->B, hipHostMallocDefault)) != hipSuccess)
-    return bail("hipHostMalloc", e);
-  c->h_seq = reinterpret_cast<uint64_t*>(c->h_pods + c->B);
-  if ((e = hipHostMalloc(&c->h_committed, COMMITTED_BYTES + sizeof(PlacementDev) * c->B, hipHostMallocDefault)) != hipSuccess)
-    return bail("hipHostMalloc", e);
-  c->h_out = reinterpret_cast<PlacementDev*>(c->h_committed + COMMITTED_BYTES / 4);
-  if ((e = hipHostMalloc(&c->h_xchg_send, xb, hipHostMallocDefault)) != hipSuccess) return bail("hipHostMalloc", e);
-  (void)hipMemset(c->d_S, 0xff, (size_t)c->B * c->ld * 2);
-  {
-    for (auto& sl : c->slot) {
-      if ((e = hipEventCreateWithFlags(&sl.ev_go, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-      if ((e = hipEventCreateWithFlags(&sl.ev_evdone, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
-    }
-    gs_ctx::Slot& s0 = c->slot[0];
-    s0.d_S = c->d_S; s0.d_aff = c->d_aff;
-    s0.d_pods = c->d_pods; s0.d_seq = c->d_seq; s0.d_out = c->d_out; s0.d_committed = c->d_committed;
-    s0.h_pods = c->h_pods; s0.h_seq = c->h_seq; s0.h_out = c->h_out; s0.h_committed = c->h_committed;
-    for (int i = 0; i < 6; ++i) s0.ev[i] = c->ev[i];
-    gs_ctx::Slot& s1 = c->slot[1];
-    s0.d_tb = c->d_tb;
-    s1.d_tb = c->d_tb + (size_t)TB_N * c->B;
-    if ((e = hipMalloc(&s1.d_S, (size_t)c->B * c->ld * 2)) != hipSuccess) return bail("hipMalloc S", e);
-    if ((e = hipMalloc(&s1.d_aff, (size_t)c->B * c->ld)) != hipSuccess) return bail("hipMalloc aff", e);
-    (void)hipMemset(s1.d_S, 0xff, (size_t)c->B * c->ld * 2);
-    if ((e = hipMalloc(&s1.d_pods, (sizeof(PodVec) + 8) * c->B)) != hipSuccess) return bail("hipMalloc", e);
-    s1.d_seq = reinterpret_cast<uint64_t*>(s1.d_pods + c->B);
-    if ((e = hipMalloc(&s1.d_committed, COMMITTED_BYTES + sizeof(PlacementDev) * c->B)) != hipSuccess) return bail("hipMalloc", e);
-    s1.d_out = reinterpret_cast<PlacementDev*>(s1.d_committed + COMMITTED_BYTES / 4);
-    if ((e = hipHostMalloc(&s1.h_pods, (sizeof(PodVec) + 8) * c->B, hipHostMallocDefault)) != hipSuccess)
-      return bail("hipHostMalloc", e);
-    s1.h_seq = reinterpret_cast<uint64_t*>(s1.h_pods + c->B);
-    if ((e = hipHostMalloc(&s1.h_committed, COMMITTED_BYTES + sizeof(PlacementDev) * c->B, hipHostMallocDefault)) != hipSuccess)
-      return bail("hipHostMalloc", e);
-    s1.h_out = reinterpret_cast<PlacementDev*>(s1.h_committed + COMMITTED_BYTES / 4);
-    for (int i = 0; i < 6; ++i)
-      if ((e = hipEventCreate(&s1.ev[i])) != hipSuccess) return bail("hipEventCreate", e);
-    c->cand_overlap = !env_off("GS_CAND_OVERLAP");
-    if (c->cand_overlap)
-      for (auto& sl : c->slot) {
-        if ((e = hipMalloc(&sl.d_lst, xb)) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMalloc(&sl.d_hist, (size_t)4 * c->B * (MAX_SCORE_LIMIT + 1))) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMalloc(&sl.d_landed, landed_slab_bytes())) != hipSuccess) return bail("hipMalloc", e);
-        (void)hipMemset(sl.d_landed, 0, landed_slab_bytes());
-      }
-    c->d_lst = s0.d_lst;
-    c->d_hist = s0.d_hist;
+  if ((e = c->d_stage_rows.alloc((size_t)(8 * ROW_WORDS + 4) * c->stage_cap)) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = c->h_stage_rows.alloc((size_t)(8 * ROW_WORDS + 4) * c->stage_cap)) != hipSuccess) return bail("hipHostMalloc", e);
+  if ((e = c->h_xchg_send.alloc(xb)) != hipSuccess) return bail("hipHostMalloc", e);
+  c->cand_overlap = !env_off("GS_CAND_OVERLAP");
+  // pods | seq and committed | out share one allocation each: one copy per batch each way
+  static_assert(sizeof(PodVec) % 8 == 0 && sizeof(PlacementDev) % 8 == 0, "staging layout");
+  const size_t pods_bytes = (sizeof(PodVec) + 8) * c->B, out_bytes = COMMITTED_BYTES + sizeof(PlacementDev) * c->B;
+  for (int k = 0; k < 2; ++k) {
+    Slot& sl = c->slot[k];
+    if ((e = sl.ev_go.create(hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = sl.ev_evdone.create(hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
+    for (Event& ev : sl.ev)
+      if ((e = ev.create()) != hipSuccess) return bail("hipEventCreate", e);
+    if ((e = sl.d_S.alloc((size_t)c->B * c->ld * 2)) != hipSuccess) return bail("hipMalloc S", e);
+    if ((e = sl.d_aff.alloc((size_t)c->B * c->ld)) != hipSuccess) return bail("hipMalloc aff", e);
+    (void)hipMemset(sl.d_S.get(), 0xff, (size_t)c->B * c->ld * 2);
+    if ((e = sl.d_pods.alloc(pods_bytes)) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = sl.h_pods.alloc(pods_bytes)) != hipSuccess) return bail("hipHostMalloc", e);
+    sl.d_seq = reinterpret_cast<uint64_t*>(sl.d_pods.get() + c->B);
+    sl.h_seq = reinterpret_cast<uint64_t*>(sl.h_pods.get() + c->B);
+    if ((e = sl.d_committed.alloc(out_bytes)) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = sl.h_committed.alloc(out_bytes)) != hipSuccess) return bail("hipHostMalloc", e);
+    sl.d_out = reinterpret_cast<PlacementDev*>(sl.d_committed.get() + COMMITTED_BYTES / 4);
+    sl.h_out = reinterpret_cast<PlacementDev*>(sl.h_committed.get() + COMMITTED_BYTES / 4);
+    sl.d_tb = c->tb_all.get() + (size_t)TB_N * c->B * k;
+    if (!c->cand_overlap) continue;
+    if ((e = sl.d_lst.alloc(xb)) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = sl.d_hist.alloc((size_t)4 * c->B * (MAX_SCORE_LIMIT + 1))) != hipSuccess) return bail("hipMalloc", e);
+    if ((e = sl.d_landed.alloc(landed_slab_bytes())) != hipSuccess) return bail("hipMalloc", e);
+    (void)hipMemset(sl.d_landed.get(), 0, landed_slab_bytes());
   }
-  if ((e = hipMalloc(&c->d_cscratch, cand_split_scratch_bytes())) != hipSuccess) return bail("hipMalloc", e);
+  if ((e = c->d_cscratch.alloc(cand_split_scratch_bytes())) != hipSuccess) return bail("hipMalloc", e);
   c->host_timing = env_on("GS_HOST_TIMING");
   if (env_on("GS_COMMIT_STAMPS")) {
     // 8 waves x 64 entries (commit_spec_kernel: one region per wave; the other commit kernels: region 0), then the
     // cand kernel's 8 at entry 512
-    if ((e = hipMalloc(&c->d_stamps, 8 * 524)) != hipSuccess) return bail("hipMalloc", e);
-    (void)hipMemset(c->d_stamps, 0, 8 * 524);
-    set_cand_stamps(c->d_stamps + 512);
+    if ((e = c->d_stamps.alloc(8 * 524)) != hipSuccess) return bail("hipMalloc", e);
+    (void)hipMemset(c->d_stamps.get(), 0, 8 * 524);
+    set_cand_stamps(c->d_stamps.get() + 512);
   }
   if ((e = hipDeviceSynchronize()) != hipSuccess) return bail("hipDeviceSynchronize", e);
   // 96 B (LoadAware + Fit row), + 192 B NodeNUMAResource columns when enabled
@@ -2309,13 +2274,9 @@ int gs_create(const gs_config* cfg, gs_ctx** out) {
   return GS_OK;
 }
 
-int gs_destroy(gs_ctx* c) {
-  if (!c) return GS_EINVAL;
-  async_stop(c);
-  if (c->watchdog.joinable()) {
-    c->wd_stop.store(true);
-    c->watchdog.join();
-  }
+namespace {
+// GS_HOST_TIMING=1: the host's time per batch of schedule_stream and per extension pod, on stderr
+void report_host_timing(const gs_ctx* c) {
   if (c->host_timing && c->ht_batches) {
     const double n = (double)c->ht_batches;
     fprintf(stderr, "gpuscore host per batch (us, %llu batches): waiting for the batch %.0f | applying placements %.0f | "
@@ -2332,174 +2293,126 @@ int gs_destroy(gs_ctx* c) {
             c->hx_prep / n, c->hx_flush / n, c->hx_gpu / n, c->hx_reserve / n, (unsigned long long)c->hx_runs,
             c->hx_runs ? c->hx_plain / (double)c->hx_runs : 0.0);
   }
-  if (c->d_dev_stage) (void)hipFree(c->d_dev_stage);
-  if (c->h_dev_stage) (void)hipHostFree(c->h_dev_stage);
-  for (void* p : {(void*)c->d_dev, (void*)c->d_xin, (void*)c->d_xtot,
-                  (void*)c->d_xds, (void*)c->d_xrs, (void*)c->d_xnom, (void*)c->d_xT, (void*)c->d_xout})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)c->h_xin, (void*)c->h_xout, (void*)c->h_xnom})
-    if (p) (void)hipHostFree(p);
-  if (c->d_stamps) {
+}
+
+// GS_COMMIT_STAMPS=1: the commit kernel's phase cycle sums, on stderr
+void report_commit_stamps(const gs_ctx* c) {
+  if (!c->d_stamps) return;
+  if (!c->window_k) {   // speculative commit kernel: one stamp region per wave
     std::vector<uint64_t> sa(524);
-    if (hipMemcpy(sa.data(), c->d_stamps, 8 * 524, hipMemcpyDeviceToHost) == hipSuccess) {
-      if (!c->window_k) {   // speculative commit kernel: one stamp region per wave
-        const double np = c->stats_all_pods ? (double)c->stats_all_pods : 1.0;
-        auto W = [&](int w, int i) { return (double)sa[w * 64 + i] / np; };
-        fprintf(stderr, "gpuscore spec commit, cycles per committed pod (%llu pods, %llu decisions, %llu rollbacks, %.0f "
-                "rollback cycles, full-row %llu):\n", (unsigned long long)c->stats_all_pods, (unsigned long long)sa[9],
-                (unsigned long long)sa[3], W(0, 4) + W(0, 37) + W(0, 38) + W(0, 39),
-                (unsigned long long)sa[10]);
-        fprintf(stderr, "  wave 0 total %.0f: checks %.0f | dirty state %.0f | hdr+fresh store+dirty loads %.0f | level scan "
-                "%.0f | winner %.0f | fresh slot %.0f | record %.0f | waiting %.0f (at batch end %.0f) | full-row %.0f\n",
-                W(0, 12), W(0, 27), W(0, 28), W(0, 29), W(0, 18), W(0, 19), W(0, 20), W(0, 0), W(0, 2), W(0, 23), W(0, 11));
-        if (sa[64 + 9] > 0)   // the split selector: wave 0 finishes the prep wave's decisions and verifies
-          fprintf(stderr, "  wave 0 (split): verification loop %.0f | fresh slot's scores + snapshot %.0f | record read + late "
-                  "decisions %.0f | exclusions %.0f | rows settled early %.0f | window %.0f | record %.0f (fresh slot %.0f) | "
-                  "waiting %.0f (the loop's passes while waiting count in the first two)\n", W(0, 55), W(0, 27), W(0, 52),
-                  W(0, 53), W(0, 54), W(0, 19), W(0, 0), W(0, 20), W(0, 2));
-        if (sa[64 + 9] > 0)
-          fprintf(stderr, "  wave 0 (split) waiting passes per pod: batch end %.2f | speculation depth %.2f | host cut %.2f | "
-                  "exact record asked %.2f | prep record not ready %.2f\n", W(0, 56), W(0, 57), W(0, 58), W(0, 59), W(0, 60));
-        fprintf(stderr, "  winner split: ties + tie-break position %.0f | old-nodes path: level segment + list window %.0f\n",
-                W(0, 30), W(0, 46));
-        if (sa[64 + 9] == 0)   // (single selector wave; the split selector reuses these entries, printed below)
-          fprintf(stderr, "  late-landing estimate: %llu decisions, previous pod's row as it stood > M %llu, == M %llu (tie-break "
-                "position moves %llu)\n", (unsigned long long)sa[47], (unsigned long long)sa[48], (unsigned long long)sa[49],
-                (unsigned long long)sa[50]);
-        fprintf(stderr, "  wave 0 raw (cycles per pod by stamp index):");
-        for (int i = 0; i < 60; ++i)
-          if (sa[i] && (i < 47 || i > 50)) fprintf(stderr, " %d=%.0f", i, W(0, i));
-        fprintf(stderr, "\n  wave 1 raw (the split selector's prep wave):");
-        for (int i = 0; i < 52; ++i)
-          if (sa[64 + i]) fprintf(stderr, " %d=%.0f", i, W(1, i));
-        fprintf(stderr, "\n  split: late landings %llu, full decisions %llu, excluded ties %llu, rows settled early %llu\n",
-                (unsigned long long)sa[47], (unsigned long long)sa[48], (unsigned long long)sa[49], (unsigned long long)sa[50]);
-        const double ng = sa[31] ? (double)sa[31] : 1.0;
-        fprintf(stderr, "  winner: old-nodes-only path %llu decisions (%.1f%%), general path %llu (%.1f%%): avg old %.1f new "
-                "%.1f window %.1f; avg dirty slots %.1f; list window beyond 32: %llu, beyond 64: %llu\n",
-                (unsigned long long)sa[36], 100.0 * sa[36] / np, (unsigned long long)sa[31], 100.0 * sa[31] / np,
-                sa[32] / (ng + sa[36]), sa[33] / ng, sa[34] / ng, sa[35] / np, (unsigned long long)sa[24],
-                (unsigned long long)sa[25]);
-        const double nr = sa[3] ? (double)sa[3] : 1.0;
-        auto R = [&](int i) { return (double)sa[i] / nr; };
-        fprintf(stderr, "  rollback (cycles per rollback): parking %.0f | undo+hash %.0f | restored-row re-scoring %.0f | "
-                "rest %.0f; restored rows %.2f, depth %.2f decisions\n", R(37), R(38), R(39), R(4), R(40), R(41));
-        fprintf(stderr, "  pending row's pre-landing score >= M: %llu decisions, %llu of the rollbacks; > M: %llu decisions, %llu "
-                "of the rollbacks\n", (unsigned long long)sa[42], (unsigned long long)sa[43], (unsigned long long)sa[44],
-                (unsigned long long)sa[45]);
-        const bool split = sa[64 + 9] > 0;   // the prep wave counted its records: the split selector ran
-        if (split)
-          fprintf(stderr, "  wave 1 (prep): busy %.0f (dirty state %.0f, loads %.0f, level scan %.0f, winner %.0f, record "
-                  "%.0f) waiting %.0f\n", W(1, 28) + W(1, 29) + W(1, 18) + W(1, 30) + W(1, 46) + W(1, 19) + W(1, 0),
-                  W(1, 28), W(1, 29), W(1, 18), W(1, 30) + W(1, 46) + W(1, 19), W(1, 0), W(1, 2));
-        else
-          fprintf(stderr, "  wave 4 (verify): busy %.0f waiting %.0f\n", W(4, 1), W(4, 2));
-        for (int w = 2; w < 4; ++w)
-          fprintf(stderr, "  wave %d (Reserve): fetch+undo %.0f numa_eval %.0f lane0 %.0f rest %.0f (fresh fetch %.0f, landed-"
-                  "again wait %.0f) waiting %.0f (first decision %.0f)\n", w, W(w, 15), W(w, 16), W(w, 17), W(w, 5), W(w, 21),
-                  W(w, 22), W(w, 6), W(w, 26));
-        for (int w : {split ? 4 : 1, 5, 6, 7})
-          fprintf(stderr, "  wave %d (re-scoring): busy %.0f (row copy + hint table %.0f, scores %.0f) waiting %.0f, jobs %.2f "
-                  "per pod\n", w, W(w, 7) + W(w, 9), W(w, 9), W(w, 7), W(w, 8), W(w, 10));
-        for (int base : {30, 40}) {   // re-scoring jobs by what their lanes needed (gs_commit_spec.hip, ST)
-          uint64_t v[8] = {};
-          for (int w : {split ? 4 : 1, 5, 6, 7})
-            for (int i = 0; i < 8; ++i) v[i] += sa[w * 64 + base + i];
-          fprintf(stderr, "  re-scoring jobs on %s rows: %llu jobs, %llu lanes: infeasible at batch start %llu, below the "
-                  "lowest listed level %llu, needed %llu, lists too short %llu; jobs with every lane infeasible %llu, with "
-                  "no lane needed %llu\n", base == 30 ? "no-policy" : "NUMA-policy", (unsigned long long)v[0],
-                  (unsigned long long)v[1], (unsigned long long)v[2], (unsigned long long)v[3], (unsigned long long)v[4],
-                  (unsigned long long)v[5], (unsigned long long)v[6], (unsigned long long)v[7]);
-        }
-        const double nb = c->stats.batches ? (double)c->stats.batches * c->B : 1.0;
-        fprintf(stderr, "gpuscore cand_kernel, wave-0 cycles per pod row: pass 1 %.0f, level sums %.0f, level pick %.0f, "
-                "offsets %.0f, pass 2 %.0f\n", sa[512] / nb, sa[513] / nb, sa[514] / nb, sa[515] / nb, sa[516] / nb);
-        fprintf(stderr, "gpuscore fix_levels_kernel, thread-0 cycles per pod row: loads+dedupe %.0f, landed rows + level pick "
-                "%.0f, lists %.0f; the block's slowest landed-row lane: row loads %.0f, loads + evaluation %.0f; thread 0: "
-                "start -> its evaluation %.0f, start -> every lane evaluated %.0f\n",
-                sa[517] / nb, sa[518] / nb, sa[519] / nb, sa[520] / nb, sa[521] / nb, sa[522] / nb, sa[523] / nb);
-        (void)hipFree(c->d_stamps);
-        c->d_stamps = nullptr;
-      }
+    if (hipMemcpy(sa.data(), c->d_stamps.get(), 8 * 524, hipMemcpyDeviceToHost) != hipSuccess) return;
+    const double np = c->stats_all_pods ? (double)c->stats_all_pods : 1.0;
+    auto W = [&](int w, int i) { return (double)sa[w * 64 + i] / np; };
+    fprintf(stderr, "gpuscore spec commit, cycles per committed pod (%llu pods, %llu decisions, %llu rollbacks, %.0f "
+            "rollback cycles, full-row %llu):\n", (unsigned long long)c->stats_all_pods, (unsigned long long)sa[9],
+            (unsigned long long)sa[3], W(0, 4) + W(0, 37) + W(0, 38) + W(0, 39),
+            (unsigned long long)sa[10]);
+    fprintf(stderr, "  wave 0 total %.0f: checks %.0f | dirty state %.0f | hdr+fresh store+dirty loads %.0f | level scan "
+            "%.0f | winner %.0f | fresh slot %.0f | record %.0f | waiting %.0f (at batch end %.0f) | full-row %.0f\n",
+            W(0, 12), W(0, 27), W(0, 28), W(0, 29), W(0, 18), W(0, 19), W(0, 20), W(0, 0), W(0, 2), W(0, 23), W(0, 11));
+    if (sa[64 + 9] > 0)   // the split selector: wave 0 finishes the prep wave's decisions and verifies
+      fprintf(stderr, "  wave 0 (split): verification loop %.0f | fresh slot's scores + snapshot %.0f | record read + late "
+              "decisions %.0f | exclusions %.0f | rows settled early %.0f | window %.0f | record %.0f (fresh slot %.0f) | "
+              "waiting %.0f (the loop's passes while waiting count in the first two)\n", W(0, 55), W(0, 27), W(0, 52),
+              W(0, 53), W(0, 54), W(0, 19), W(0, 0), W(0, 20), W(0, 2));
+    if (sa[64 + 9] > 0)
+      fprintf(stderr, "  wave 0 (split) waiting passes per pod: batch end %.2f | speculation depth %.2f | host cut %.2f | "
+              "exact record asked %.2f | prep record not ready %.2f\n", W(0, 56), W(0, 57), W(0, 58), W(0, 59), W(0, 60));
+    fprintf(stderr, "  winner split: ties + tie-break position %.0f | old-nodes path: level segment + list window %.0f\n",
+            W(0, 30), W(0, 46));
+    if (sa[64 + 9] == 0)   // (single selector wave; the split selector reuses these entries, printed below)
+      fprintf(stderr, "  late-landing estimate: %llu decisions, previous pod's row as it stood > M %llu, == M %llu (tie-break "
+            "position moves %llu)\n", (unsigned long long)sa[47], (unsigned long long)sa[48], (unsigned long long)sa[49],
+            (unsigned long long)sa[50]);
+    fprintf(stderr, "  wave 0 raw (cycles per pod by stamp index):");
+    for (int i = 0; i < 60; ++i)
+      if (sa[i] && (i < 47 || i > 50)) fprintf(stderr, " %d=%.0f", i, W(0, i));
+    fprintf(stderr, "\n  wave 1 raw (the split selector's prep wave):");
+    for (int i = 0; i < 52; ++i)
+      if (sa[64 + i]) fprintf(stderr, " %d=%.0f", i, W(1, i));
+    fprintf(stderr, "\n  split: late landings %llu, full decisions %llu, excluded ties %llu, rows settled early %llu\n",
+            (unsigned long long)sa[47], (unsigned long long)sa[48], (unsigned long long)sa[49], (unsigned long long)sa[50]);
+    const double ng = sa[31] ? (double)sa[31] : 1.0;
+    fprintf(stderr, "  winner: old-nodes-only path %llu decisions (%.1f%%), general path %llu (%.1f%%): avg old %.1f new "
+            "%.1f window %.1f; avg dirty slots %.1f; list window beyond 32: %llu, beyond 64: %llu\n",
+            (unsigned long long)sa[36], 100.0 * sa[36] / np, (unsigned long long)sa[31], 100.0 * sa[31] / np,
+            sa[32] / (ng + sa[36]), sa[33] / ng, sa[34] / ng, sa[35] / np, (unsigned long long)sa[24],
+            (unsigned long long)sa[25]);
+    const double nr = sa[3] ? (double)sa[3] : 1.0;
+    auto R = [&](int i) { return (double)sa[i] / nr; };
+    fprintf(stderr, "  rollback (cycles per rollback): parking %.0f | undo+hash %.0f | restored-row re-scoring %.0f | "
+            "rest %.0f; restored rows %.2f, depth %.2f decisions\n", R(37), R(38), R(39), R(4), R(40), R(41));
+    fprintf(stderr, "  pending row's pre-landing score >= M: %llu decisions, %llu of the rollbacks; > M: %llu decisions, %llu "
+            "of the rollbacks\n", (unsigned long long)sa[42], (unsigned long long)sa[43], (unsigned long long)sa[44],
+            (unsigned long long)sa[45]);
+    const bool split = sa[64 + 9] > 0;   // the prep wave counted its records: the split selector ran
+    if (split)
+      fprintf(stderr, "  wave 1 (prep): busy %.0f (dirty state %.0f, loads %.0f, level scan %.0f, winner %.0f, record "
+              "%.0f) waiting %.0f\n", W(1, 28) + W(1, 29) + W(1, 18) + W(1, 30) + W(1, 46) + W(1, 19) + W(1, 0),
+              W(1, 28), W(1, 29), W(1, 18), W(1, 30) + W(1, 46) + W(1, 19), W(1, 0), W(1, 2));
+    else
+      fprintf(stderr, "  wave 4 (verify): busy %.0f waiting %.0f\n", W(4, 1), W(4, 2));
+    for (int w = 2; w < 4; ++w)
+      fprintf(stderr, "  wave %d (Reserve): fetch+undo %.0f numa_eval %.0f lane0 %.0f rest %.0f (fresh fetch %.0f, landed-"
+              "again wait %.0f) waiting %.0f (first decision %.0f)\n", w, W(w, 15), W(w, 16), W(w, 17), W(w, 5), W(w, 21),
+              W(w, 22), W(w, 6), W(w, 26));
+    for (int w : {split ? 4 : 1, 5, 6, 7})
+      fprintf(stderr, "  wave %d (re-scoring): busy %.0f (row copy + hint table %.0f, scores %.0f) waiting %.0f, jobs %.2f "
+              "per pod\n", w, W(w, 7) + W(w, 9), W(w, 9), W(w, 7), W(w, 8), W(w, 10));
+    for (int base : {30, 40}) {   // re-scoring jobs by what their lanes needed (gs_commit_spec.hip, ST)
+      uint64_t v[8] = {};
+      for (int w : {split ? 4 : 1, 5, 6, 7})
+        for (int i = 0; i < 8; ++i) v[i] += sa[w * 64 + base + i];
+      fprintf(stderr, "  re-scoring jobs on %s rows: %llu jobs, %llu lanes: infeasible at batch start %llu, below the "
+              "lowest listed level %llu, needed %llu, lists too short %llu; jobs with every lane infeasible %llu, with "
+              "no lane needed %llu\n", base == 30 ? "no-policy" : "NUMA-policy", (unsigned long long)v[0],
+              (unsigned long long)v[1], (unsigned long long)v[2], (unsigned long long)v[3], (unsigned long long)v[4],
+              (unsigned long long)v[5], (unsigned long long)v[6], (unsigned long long)v[7]);
     }
-  }
-  if (c->d_stamps) {
+    const double nb = c->stats.batches ? (double)c->stats.batches * c->B : 1.0;
+    fprintf(stderr, "gpuscore cand_kernel, wave-0 cycles per pod row: pass 1 %.0f, level sums %.0f, level pick %.0f, "
+            "offsets %.0f, pass 2 %.0f\n", sa[512] / nb, sa[513] / nb, sa[514] / nb, sa[515] / nb, sa[516] / nb);
+    fprintf(stderr, "gpuscore fix_levels_kernel, thread-0 cycles per pod row: loads+dedupe %.0f, landed rows + level pick "
+            "%.0f, lists %.0f; the block's slowest landed-row lane: row loads %.0f, loads + evaluation %.0f; thread 0: "
+            "start -> its evaluation %.0f, start -> every lane evaluated %.0f\n",
+            sa[517] / nb, sa[518] / nb, sa[519] / nb, sa[520] / nb, sa[521] / nb, sa[522] / nb, sa[523] / nb);
+  } else {   // the lockstep commit kernel (node sampling): region 0
     uint64_t st[32] = {};
-    if (hipMemcpy(st, c->d_stamps, 256, hipMemcpyDeviceToHost) == hipSuccess) {
-      uint64_t tot = 0;
-      for (int i = 0; i < 12; ++i) tot += st[i];
-      fprintf(stderr, "gpuscore commit phases (s_memtime ticks, %% of %llu):", (unsigned long long)tot);
-      for (int i = 0; i < 12; ++i) fprintf(stderr, " p%d=%.1f%%", i, tot ? 100.0 * st[i] / tot : 0.0);
-      fprintf(stderr, "\n  raw ticks per committed pod (%llu pods):", (unsigned long long)c->stats_all_pods);
-      for (int i = 0; i < 22; ++i)
-        fprintf(stderr, " s%d=%.0f", i, c->stats_all_pods ? (double)st[i] / (double)c->stats_all_pods : 0.0);
-      fprintf(stderr, "\n  pods through full-row resolution %llu, FitError %llu, slow path %llu",
-              (unsigned long long)st[18], (unsigned long long)st[19], (unsigned long long)st[20]);
-      fprintf(stderr, ", winners on NUMA-policy rows %llu, fresh winners %llu, cpuset pods %llu | s24 (Reserve pair "
-              "evaluation) %.0f", (unsigned long long)st[22], (unsigned long long)st[23], (unsigned long long)st[25],
-              c->stats_all_pods ? (double)st[24] / (double)c->stats_all_pods : 0.0);
-      fprintf(stderr, " | s26 (full-row resolution, per such pod) %.0f", st[18] ? (double)st[26] / (double)st[18] : 0.0);
-      fprintf(stderr, " | policy-row rescoring: %llu pods, %.0f ticks per pair (thread 128)\n",
-              (unsigned long long)st[12], st[12] ? (double)st[13] / st[12] : 0.0);
-    }
-    (void)hipFree(c->d_stamps);
+    if (hipMemcpy(st, c->d_stamps.get(), 256, hipMemcpyDeviceToHost) != hipSuccess) return;
+    uint64_t tot = 0;
+    for (int i = 0; i < 12; ++i) tot += st[i];
+    fprintf(stderr, "gpuscore commit phases (s_memtime ticks, %% of %llu):", (unsigned long long)tot);
+    for (int i = 0; i < 12; ++i) fprintf(stderr, " p%d=%.1f%%", i, tot ? 100.0 * st[i] / tot : 0.0);
+    fprintf(stderr, "\n  raw ticks per committed pod (%llu pods):", (unsigned long long)c->stats_all_pods);
+    for (int i = 0; i < 22; ++i)
+      fprintf(stderr, " s%d=%.0f", i, c->stats_all_pods ? (double)st[i] / (double)c->stats_all_pods : 0.0);
+    fprintf(stderr, "\n  pods through full-row resolution %llu, FitError %llu, slow path %llu",
+            (unsigned long long)st[18], (unsigned long long)st[19], (unsigned long long)st[20]);
+    fprintf(stderr, ", winners on NUMA-policy rows %llu, fresh winners %llu, cpuset pods %llu | s24 (Reserve pair "
+            "evaluation) %.0f", (unsigned long long)st[22], (unsigned long long)st[23], (unsigned long long)st[25],
+            c->stats_all_pods ? (double)st[24] / (double)c->stats_all_pods : 0.0);
+    fprintf(stderr, " | s26 (full-row resolution, per such pod) %.0f", st[18] ? (double)st[26] / (double)st[18] : 0.0);
+    fprintf(stderr, " | policy-row rescoring: %llu pods, %.0f ticks per pair (thread 128)\n",
+            (unsigned long long)st[12], st[12] ? (double)st[13] / st[12] : 0.0);
   }
+}
+}  // namespace
+
+// Stop what still uses the context (worker, watchdog), report, then wait for every stream before the members go
+// (gs_ctx: buffers, then events, then streams). Also the way out of a half-built context (gs_create's bail).
+int gs_destroy(gs_ctx* c) {
+  if (!c) return GS_EINVAL;
+  async_stop(c);
+  if (c->watchdog.joinable()) {
+    c->wd_stop.store(true);
+    c->watchdog.join();
+  }
+  report_host_timing(c);
+  report_commit_stamps(c);
   if (c->comm) ncclCommDestroy(c->comm);
-  if (c->lg_ready) (void)hipEventDestroy(c->lg_ready);
-  if (c->lg_done) (void)hipEventDestroy(c->lg_done);
-  for (hipEvent_t ev : c->x_ev) (void)hipEventDestroy(ev);
-  if (c->st) (void)host_wait_stream(c->st);
-  if (c->st_ev) (void)host_wait_stream(c->st_ev);
-  if (c->st_rb) (void)host_wait_stream(c->st_rb);   // readbacks into the pinned buffers freed below
-  if (c->slot[0].d_pods) bind_slot(c, 0);
-  {
-    gs_ctx::Slot& s1 = c->slot[1];
-    for (auto& sl : c->slot) {
-      if (sl.ev_go) (void)hipEventDestroy(sl.ev_go);
-      if (sl.ev_evdone) (void)hipEventDestroy(sl.ev_evdone);
-    }
-      for (auto& sl : c->slot) {
-      if (sl.d_lst) (void)hipFree(sl.d_lst);
-      if (sl.d_hist) (void)hipFree(sl.d_hist);
-      if (sl.d_landed) (void)hipFree(sl.d_landed);
-      sl.d_lst = nullptr;
-      sl.d_hist = nullptr;
-      sl.d_landed = nullptr;
-    }
-    c->d_lst = nullptr;
-    c->d_hist = nullptr;
-    if (c->d_cscratch) (void)hipFree(c->d_cscratch);
-    c->d_cscratch = nullptr;
-    void* d1[] = {s1.d_pods, s1.d_committed, s1.d_S, s1.d_aff};   // (seq / out live inside pods / committed)
-    for (void* p : d1)
-      if (p) (void)hipFree(p);
-    void* h1[] = {s1.h_pods, s1.h_committed};
-    for (void* p : h1)
-      if (p) (void)hipHostFree(p);
-    for (auto& ev : s1.ev)
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  void* dev[] = {c->d_xerr, c->d_xsmall,
-                 c->d_i64, c->d_i32, c->d_pods, c->d_S, c->d_xchg_send, c->d_xchg_recv, c->d_xmerged,
-                 c->d_committed, c->d_rowstat, c->d_sel, c->d_stage_idx, c->d_stage_rows, c->d_numa_idx, c->d_xnuma_idx,
-                 c->d_topos, c->d_aff, c->d_tb, c->d_sx_send, c->d_sx_recv};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  void* host[] = {c->h_sx_send, c->h_sx_recv, c->h_xsmall, c->h_pods, c->h_committed, c->h_stage_idx, c->h_stage_rows, c->h_xchg_send,
-                  c->h_xchg_recv};
-  for (void* p : host)
-    if (p) (void)hipHostFree(p);
-  for (auto& ev : c->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  if (c->st_ev) (void)hipStreamDestroy(c->st_ev);
-  if (c->st_rb) (void)hipStreamDestroy(c->st_rb);
-  if (c->slab_mv.i64) (void)hipFree(c->slab_mv.i64);
-  if (c->slab_mv.i32) (void)hipFree(c->slab_mv.i32);
-  if (c->st2) (void)host_wait_stream(c->st2);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->st2) (void)hipStreamDestroy(c->st2);
-  if (c->st) (void)hipStreamDestroy(c->st);
+  // readbacks into the pinned buffers and the side stream's eval pass may still be in flight
+  for (const Stream* s : {&c->st, &c->st_ev, &c->st_rb, &c->st2})
+    if (*s) (void)host_wait_stream(s->get());
   delete c;
   return GS_OK;
 }
@@ -2658,32 +2571,33 @@ int gs_evaluate(gs_ctx* c, const gs_pod* pods, uint32_t npods, int16_t* scores, 
   if ((rc = node_prep(c))) return rc;
   const uint32_t N = c->N;
   const int chunk = c->B;
-  int16_t *d_sc = nullptr, *d_pl = nullptr;
-  uint16_t* d_cd = nullptr;
-  HIP_TRY(c, hipMalloc(&d_sc, (size_t)chunk * N * 2));
-  HIP_TRY(c, hipMalloc(&d_cd, (size_t)chunk * N * 2));
-  HIP_TRY(c, hipMalloc(&d_pl, (size_t)chunk * N * 2 * GS_NUM_PLUGINS));
+  DevBuf<int16_t> d_sc, d_pl;   // (released on every way out)
+  DevBuf<uint16_t> d_cd;
+  HIP_TRY(c, d_sc.alloc((size_t)chunk * N * 2));
+  HIP_TRY(c, d_cd.alloc((size_t)chunk * N * 2));
+  HIP_TRY(c, d_pl.alloc((size_t)chunk * N * 2 * GS_NUM_PLUGINS));
+  const Slot& s = current_slot(c);   // no batch is in flight: its pod staging buffers serve the chunks
+  PodVec *const h_pods = s.h_pods.get(), *const d_pods = s.d_pods.get();
+  const hipStream_t st = c->st.get();
   for (uint32_t p0 = 0; p0 < npods; p0 += chunk) {
     int b = (int)std::min<uint32_t>(chunk, npods - p0);
     int prod_cols = 0;
     for (int i = 0; i < b; ++i) {
       if ((rc = validate_pod(c, pods[p0 + i]))) break;
-      c->h_pods[i] = prep_pod(c, pods[p0 + i]);
-      prod_cols |= (c->h_pods[i].flags & PF_PROD_SCORE) ? 1 : 0;
+      h_pods[i] = prep_pod(c, pods[p0 + i]);
+      prod_cols |= (h_pods[i].flags & PF_PROD_SCORE) ? 1 : 0;
     }
     if (rc) break;
-    HIP_TRY(c, hipMemcpyAsync(c->d_pods, c->h_pods, sizeof(PodVec) * b, hipMemcpyHostToDevice, c->st));
-    HIP_TRY(c, launch_eval_full(c->mv, c->d_pods, b, c->pf, N, d_sc, d_cd, d_pl, prod_cols, c->st));
-    if (scores) HIP_TRY(c, hipMemcpyAsync(scores + (size_t)p0 * N, d_sc, (size_t)b * N * 2, hipMemcpyDeviceToHost, c->st));
-    if (codes) HIP_TRY(c, hipMemcpyAsync(codes + (size_t)p0 * N, d_cd, (size_t)b * N * 2, hipMemcpyDeviceToHost, c->st));
+    HIP_TRY(c, hipMemcpyAsync(d_pods, h_pods, sizeof(PodVec) * b, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, launch_eval_full(c->mv, d_pods, b, c->pf, N, d_sc.get(), d_cd.get(), d_pl.get(), prod_cols, st));
+    if (scores)
+      HIP_TRY(c, hipMemcpyAsync(scores + (size_t)p0 * N, d_sc.get(), (size_t)b * N * 2, hipMemcpyDeviceToHost, st));
+    if (codes) HIP_TRY(c, hipMemcpyAsync(codes + (size_t)p0 * N, d_cd.get(), (size_t)b * N * 2, hipMemcpyDeviceToHost, st));
     if (plugin_scores)
-      HIP_TRY(c, hipMemcpyAsync(plugin_scores + (size_t)p0 * N * GS_NUM_PLUGINS, d_pl, (size_t)b * N * 2 * GS_NUM_PLUGINS,
-                                hipMemcpyDeviceToHost, c->st));
-    HIP_TRY(c, host_wait_stream(c->st));
+      HIP_TRY(c, hipMemcpyAsync(plugin_scores + (size_t)p0 * N * GS_NUM_PLUGINS, d_pl.get(),
+                                (size_t)b * N * 2 * GS_NUM_PLUGINS, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, host_wait_stream(st));
   }
-  (void)hipFree(d_sc);
-  (void)hipFree(d_cd);
-  (void)hipFree(d_pl);
   return rc;
 }
 
@@ -2698,27 +2612,27 @@ int batch_len(const gs_ctx* c, const gs_pod* pods, uint32_t i, uint32_t npods, b
   return b;
 }
 
-// PreFilter of pods [i, i+b) into the bound slot, and their upload
+// PreFilter of pods [i, i+b) into slot s, and their upload
 // (uploads on st_ev, where the batch's eval pass runs; a non-speculative batch's eval first waits for everything
 // enqueued on st — row deltas, node prep, the previous commit — a speculative one only for the eval pass before it)
-int stage_batch(gs_ctx* c, const gs_pod* pods, const uint64_t* seq, uint32_t i, int b, bool speculative) {
+int stage_batch(gs_ctx* c, Slot& s, const gs_pod* pods, const uint64_t* seq, uint32_t i, int b, bool speculative) {
+  PodVec *const h_pods = s.h_pods.get(), *const d_pods = s.d_pods.get();
   for (int j = 0; j < b; ++j) {
-    c->h_pods[j] = prep_pod(c, pods[i + j]);
-    c->h_seq[j] = seq ? seq[i + j] : (uint64_t)(i + j);
+    h_pods[j] = prep_pod(c, pods[i + j]);
+    s.h_seq[j] = seq ? seq[i + j] : (uint64_t)(i + j);
   }
   if (!speculative) {
-    const gs_ctx::Slot& sl = c->slot[c->cur_slot];
-    HIP_TRY(c, hipEventRecord(sl.ev_go, c->st));
-    HIP_TRY(c, hipStreamWaitEvent(c->st_ev, sl.ev_go, 0));
+    HIP_TRY(c, hipEventRecord(s.ev_go.get(), c->st.get()));
+    HIP_TRY(c, hipStreamWaitEvent(c->st_ev.get(), s.ev_go.get(), 0));
   }
   // one copy: the B pod vectors' block (b of them staged) and the b sequence numbers after it
-  hipStream_t up = direct_batch(c, b, speculative) ? c->st : c->st_ev;
+  hipStream_t up = direct_batch(c, b, speculative) ? c->st.get() : c->st_ev.get();
   // (the merged copy spans all B pod vectors, d_seq following the block: a short batch copies its b vectors and seq)
   if (4 * b >= c->B) {
-    HIP_TRY(c, hipMemcpyAsync(c->d_pods, c->h_pods, sizeof(PodVec) * c->B + 8 * b, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(d_pods, h_pods, sizeof(PodVec) * c->B + 8 * b, hipMemcpyHostToDevice, up));
   } else {
-    HIP_TRY(c, hipMemcpyAsync(c->d_pods, c->h_pods, sizeof(PodVec) * b, hipMemcpyHostToDevice, up));
-    HIP_TRY(c, hipMemcpyAsync(c->d_seq, c->h_seq, 8 * b, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(d_pods, h_pods, sizeof(PodVec) * b, hipMemcpyHostToDevice, up));
+    HIP_TRY(c, hipMemcpyAsync(s.d_seq, s.h_seq, 8 * b, hipMemcpyHostToDevice, up));
   }
   return GS_OK;
 }
@@ -2753,7 +2667,7 @@ struct PodRun {
 int agree_next_run(gs_ctx* c, bool* use) {
   const uint32_t mine = *use ? 1u : 0u;
   std::vector<uint32_t> all(c->nranks);
-  if (int rc = exchange_small(c, XSITE_RUNS, nullptr, 4, all.data(), c->sgather ? c->st_ev : c->st, &mine)) return rc;
+  if (int rc = exchange_small(c, XSITE_RUNS, nullptr, 4, all.data(), c->sgather ? c->st_ev.get() : c->st.get(), &mine)) return rc;
   for (uint32_t v : all) *use = *use && v;
   return GS_OK;
 }
@@ -2773,9 +2687,9 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
   bool have_nxt = false;
   auto drain = [&]() {
     Where w_(c, "schedule_stream: drain");
-    (void)host_wait_stream(c->st);
-    (void)host_wait_stream(c->st_ev);
-    (void)host_wait_stream(c->st_rb);   // a voided or in-flight batch's readback into the pinned buffers
+    (void)host_wait_stream(c->st.get());
+    (void)host_wait_stream(c->st_ev.get());
+    (void)host_wait_stream(c->st_rb.get());   // a voided or in-flight batch's readback into the pinned buffers
   };
   auto apply_batch = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
                          bool special) -> int {
@@ -2827,14 +2741,17 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         continue;
       }
       const gs_pod* pods = run.pods;
+      // the current batch's slot, and the other one for the batch after it (keeping that batch flips cur_slot below)
+      Slot& cur = c->slot[c->cur_slot];
+      Slot& ahead = c->slot[1 - c->cur_slot];
       if (!inflight) {
         if ((rc = apply_pending())) { drain(); return rc; }
         if ((rc = flush_rows(c))) return rc;
         if (c->prep_stale && (rc = node_prep(c))) return rc;
         cur_b = batch_len(c, pods, i, run.n, &cur_special);
         // (a cpuset pod whose node is outside the device cpuset scope ends the batch inside the commit kernel)
-        if ((rc = stage_batch(c, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur_b, nullptr))) return rc;
+        if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b))) return rc;
       }
       // the batch after this one: in this run, or the first of the next run
       const gs_pod* np = nullptr;
@@ -2862,13 +2779,9 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         bool sf = false;
         nb = batch_len(c, np, nj, nn, &sf);
         if (!sf && !uid_overlap(pods + i, cur_b, np + nj, nb)) {
-          const int32_t* prev = c->d_committed;
-          const PlacementDev* prev_out = c->d_out;
-          const int here = c->cur_slot;
-          bind_slot(c, 1 - here);
-          rc = stage_batch(c, np, ns, nj, nb, true);
+          rc = stage_batch(c, ahead, np, ns, nj, nb, true);
           const auto t_b = hclk::now();
-          if (!rc) rc = launch_batch(c, nb, prev, prev_out, cur_b);
+          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b);
           if (c->host_timing) {
             const double st = std::chrono::duration<double, std::micro>(t_b - t_a).count();
             const double la = std::chrono::duration<double, std::micro>(hclk::now() - t_b).count();
@@ -2876,7 +2789,6 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
             c->ht_launch += la;
             busy += st + la;
           }
-          bind_slot(c, here);
           if (rc) { drain(); return rc; }
           spec = true;
         }
@@ -2886,29 +2798,31 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       spec_ok = true;
       int committed = 0;
       const auto t_w = hclk::now();
-      rc = finish_batch(c, cur_b, spec, &committed);
+      rc = finish_batch(c, cur, cur_b, spec, &committed);
       const auto t_f = hclk::now();
       if (rc == GS_REDO) {   // pod 0 needs the full-row path, the speculative pass (void) overwrote its lists: re-run
         drain();
         if ((rc = apply_pending())) return rc;
-        if ((rc = stage_batch(c, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur_b, nullptr))) return rc;
+        if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b))) return rc;
         inflight = true;
         spec_ok = false;
         continue;
       }
       if (rc) { if (spec) drain(); return rc; }
-      const bool host_work = c->h_committed[1] != 1;   // the device-side continuation flag the speculative pass read
+      const PodVec* h_pods = cur.h_pods.get();
+      // the device-side continuation flag the speculative pass read
+      const bool host_work = cur.h_committed.get()[1] != 1;
       if (spec && !host_work && !cur_special && committed == cur_b) {
         // no host row changes: keep the results (this slot's buffers are reused by the batch two ahead) and apply them
         // after that batch is launched
-        pend_out.assign(c->h_out, c->h_out + committed);
-        pend_pods.assign(c->h_pods, c->h_pods + committed);
+        pend_out.assign(cur.h_out, cur.h_out + committed);
+        pend_pods.assign(h_pods, h_pods + committed);
         pend.pods = pods + i;
         pend.out = run.out + i;
         pend.n = committed;
         pend.active = true;
-      } else if ((rc = apply_batch(pods + i, run.out + i, committed, c->h_out, c->h_pods, cur_special))) {
+      } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special))) {
         if (spec) drain();
         return rc;
       }
@@ -2932,7 +2846,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
             drain();
             return fail(c, GS_ESTATE, "speculative batch ran while host rows were pending");
           }
-          bind_slot(c, 1 - c->cur_slot);
+          c->cur_slot = 1 - c->cur_slot;   // the speculative batch is now the current one
           cur_b = nb;
           cur_special = false;
           inflight = true;   // (when it is the next run's first batch, i == run.n: the top of the loop moves there)
@@ -3121,10 +3035,9 @@ int gs_topology_register(gs_ctx* c, const gs_cpu_topology* t, int32_t* id) {
   // device copy of every registered topology's TopoDev (index = topology id)
   std::vector<TopoDev> all(c->topos.size());
   for (size_t i = 0; i < all.size(); ++i) all[i] = c->topos[i]->dev;
-  HIP_TRY(c, host_wait_stream(c->st));
-  if (c->d_topos) { (void)hipFree(c->d_topos); c->d_topos = nullptr; }
-  HIP_TRY(c, hipMalloc(&c->d_topos, sizeof(TopoDev) * all.size()));
-  HIP_TRY(c, hipMemcpy(c->d_topos, all.data(), sizeof(TopoDev) * all.size(), hipMemcpyHostToDevice));
+  HIP_TRY(c, host_wait_stream(c->st.get()));
+  HIP_TRY(c, c->d_topos.alloc(sizeof(TopoDev) * all.size()));   // (frees the old copy: the wait above covers it)
+  HIP_TRY(c, hipMemcpy(c->d_topos.get(), all.data(), sizeof(TopoDev) * all.size(), hipMemcpyHostToDevice));
   return GS_OK;
 }
 
@@ -3276,8 +3189,8 @@ int gs_comm_init_local(gs_ctx* c, gs_local_group* g, int rank) {
   if (c->window_k && g->n > 1 && xchg_levels())
     return fail(c, GS_EUNSUPPORTED, "node sampling on several ranks needs the score-row exchange");
   HIP_TRY(c, hipSetDevice(c->cfg.device));
-  if (!c->lg_ready) HIP_TRY(c, hipEventCreateWithFlags(&c->lg_ready, hipEventDisableTiming));
-  if (!c->lg_done) HIP_TRY(c, hipEventCreateWithFlags(&c->lg_done, hipEventDisableTiming));
+  if (!c->lg_ready) HIP_TRY(c, c->lg_ready.create(hipEventDisableTiming));
+  if (!c->lg_done) HIP_TRY(c, c->lg_done.create(hipEventDisableTiming));
   c->lg = g;
   c->nranks = g->n;
   c->rank = rank;
@@ -3308,9 +3221,9 @@ int gs_reset_stats(gs_ctx* c) {
 int gs_synchronize(gs_ctx* c) {
   if (!c) return GS_EINVAL;
   quiesce(c);
-  HIP_TRY(c, host_wait_stream(c->st_ev));
-  HIP_TRY(c, host_wait_stream(c->st));
-  HIP_TRY(c, host_wait_stream(c->st_rb));
+  HIP_TRY(c, host_wait_stream(c->st_ev.get()));
+  HIP_TRY(c, host_wait_stream(c->st.get()));
+  HIP_TRY(c, host_wait_stream(c->st_rb.get()));
   return GS_OK;
 }
 
@@ -3319,10 +3232,10 @@ int gs_synchronize(gs_ctx* c) {
 int gs_reset(gs_ctx* c) {
   if (!c) return GS_EINVAL;
   quiesce(c);
-  (void)host_wait_stream(c->st);
-  (void)host_wait_stream(c->st_ev);
-  (void)host_wait_stream(c->st2);
-  (void)host_wait_stream(c->st_rb);
+  (void)host_wait_stream(c->st.get());
+  (void)host_wait_stream(c->st_ev.get());
+  (void)host_wait_stream(c->st2.get());
+  (void)host_wait_stream(c->st_rb.get());
   (void)hipGetLastError();
   for (uint32_t i = 0; i < c->N; ++i)
     if (c->nodes[i].valid) mark_dirty(c, i);
@@ -3333,7 +3246,7 @@ int gs_reset(gs_ctx* c) {
   if (!rc) rc = ext_flush_devices(c);
   if (rc) return rc;
   if ((rc = node_prep(c))) return rc;
-  hipError_t e = host_wait_stream(c->st);
+  hipError_t e = host_wait_stream(c->st.get());
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "reset: the device is unusable (%s): destroy and recreate the context",
                                    hipGetErrorString(e));
   c->err.clear();
@@ -3367,26 +3280,27 @@ int gs_debug_pair_probe(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uin
     pv[i] = prep_pod(c, pods[i]);
     prod_cols |= (pv[i].flags & PF_PROD_SCORE) ? 1 : 0;
   }
-  PodVec* d_p = nullptr;
-  uint32_t* d_n = nullptr;
-  int32_t *d_o = nullptr, *d_s = nullptr;
-  uint64_t* d_c = nullptr;
+  DevBuf<PodVec> d_p;
+  DevBuf<uint32_t> d_n;
+  DevBuf<int32_t> d_o, d_s;
+  DevBuf<uint64_t> d_c;
   const size_t ns = (size_t)n * (mode == 1 ? 64 : 1);
-  hipError_t e = hipMalloc(&d_p, sizeof(PodVec) * npods);
-  if (e == hipSuccess) e = hipMalloc(&d_n, 4 * n);
-  if (e == hipSuccess) e = hipMalloc(&d_o, 4 * n);
-  if (e == hipSuccess) e = hipMalloc(&d_s, 4 * ns);
-  if (e == hipSuccess) e = hipMalloc(&d_c, 80 * n);
-  if (e == hipSuccess) e = hipMemset(d_c, 0, 80 * n);
-  if (e == hipSuccess) e = hipMemcpy(d_p, pv.data(), sizeof(PodVec) * npods, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_n, nodes, 4 * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_o, pod_of, 4 * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = host_wait_stream(c->st);
-  if (e == hipSuccess) e = launch_probe(mode, c->mv, c->pf, d_p, (int)npods, d_n, d_o, n, prod_cols, d_s, d_c, c->st);
-  if (e == hipSuccess) e = host_wait_stream(c->st);
-  if (e == hipSuccess) e = hipMemcpy(scores, d_s, 4 * ns, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(cycles, d_c, 80 * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d_p); (void)hipFree(d_n); (void)hipFree(d_o); (void)hipFree(d_s); (void)hipFree(d_c);
+  hipError_t e = d_p.alloc(sizeof(PodVec) * npods);
+  if (e == hipSuccess) e = d_n.alloc(4 * n);
+  if (e == hipSuccess) e = d_o.alloc(4 * n);
+  if (e == hipSuccess) e = d_s.alloc(4 * ns);
+  if (e == hipSuccess) e = d_c.alloc(80 * n);
+  if (e == hipSuccess) e = hipMemset(d_c.get(), 0, 80 * n);
+  if (e == hipSuccess) e = hipMemcpy(d_p.get(), pv.data(), sizeof(PodVec) * npods, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_n.get(), nodes, 4 * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_o.get(), pod_of, 4 * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = host_wait_stream(c->st.get());
+  if (e == hipSuccess)
+    e = launch_probe(mode, c->mv, c->pf, d_p.get(), (int)npods, d_n.get(), d_o.get(), n, prod_cols, d_s.get(), d_c.get(),
+                     c->st.get());
+  if (e == hipSuccess) e = host_wait_stream(c->st.get());
+  if (e == hipSuccess) e = hipMemcpy(scores, d_s.get(), 4 * ns, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(cycles, d_c.get(), 80 * n, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "probe: %s", hipGetErrorString(e));
   return GS_OK;
 }
@@ -3400,17 +3314,15 @@ int gs_debug_numa_merge(gs_ctx* c, const gs_merge_case* cases, uint32_t n, gs_me
         cases[i].policy > GS_NUMA_POLICY_SINGLE_NUMA_NODE)
       return GS_EINVAL;
   if (!n) return GS_OK;   // (no mirror state involved: the merge's inputs are the cases)
-  gs_merge_case* d_c = nullptr;
-  gs_merge_result* d_o = nullptr;
-  hipError_t e = hipMalloc(&d_c, sizeof(gs_merge_case) * n);
-  if (e == hipSuccess) e = hipMalloc(&d_o, sizeof(gs_merge_result) * n);
-  if (e == hipSuccess) e = hipMemcpy(d_c, cases, sizeof(gs_merge_case) * n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = host_wait_stream(c->st);
-  if (e == hipSuccess) e = launch_merge_probe(d_c, (int)n, d_o, c->st);
-  if (e == hipSuccess) e = host_wait_stream(c->st);
-  if (e == hipSuccess) e = hipMemcpy(out, d_o, sizeof(gs_merge_result) * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d_c);
-  (void)hipFree(d_o);
+  DevBuf<gs_merge_case> d_c;
+  DevBuf<gs_merge_result> d_o;
+  hipError_t e = d_c.alloc(sizeof(gs_merge_case) * n);
+  if (e == hipSuccess) e = d_o.alloc(sizeof(gs_merge_result) * n);
+  if (e == hipSuccess) e = hipMemcpy(d_c.get(), cases, sizeof(gs_merge_case) * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = host_wait_stream(c->st.get());
+  if (e == hipSuccess) e = launch_merge_probe(d_c.get(), (int)n, d_o.get(), c->st.get());
+  if (e == hipSuccess) e = host_wait_stream(c->st.get());
+  if (e == hipSuccess) e = hipMemcpy(out, d_o.get(), sizeof(gs_merge_result) * n, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "merge probe: %s", hipGetErrorString(e));
   return GS_OK;
 }
@@ -3423,9 +3335,9 @@ int gs_debug_mirror_check(gs_ctx* c) {
   if (rc) return rc;
   std::vector<int64_t> d64((size_t)c->npad * NUM_I64_COLS);
   std::vector<int32_t> d32((size_t)c->npad * NUM_I32_COLS);
-  HIP_TRY(c, host_wait_stream(c->st));
-  HIP_TRY(c, hipMemcpy(d64.data(), c->d_i64, d64.size() * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemcpy(d32.data(), c->d_i32, d32.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(c, host_wait_stream(c->st.get()));
+  HIP_TRY(c, hipMemcpy(d64.data(), c->mv.i64, d64.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(d32.data(), c->mv.i32, d32.size() * 4, hipMemcpyDeviceToHost));
   int bad = 0;
   std::vector<int64_t> row(ROW_WORDS);
   for (uint32_t i = 0; i < c->N; ++i) {

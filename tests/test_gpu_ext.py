@@ -187,6 +187,59 @@ def test_c5_gpu_owner_pods_reservations_on_policy_nodes_cpuset_pods(policy_pct):
         assert (a is None) == (b is None) and (a is None or a.tobytes() == b.tobytes()), j
 
 
+@pytest.mark.parametrize("k", [1, 2, 3, 4])
+def test_scratch_borrowers_on_either_batch_slot(k):
+    """gs_evaluate and the extension path borrow the buffers and events of whichever of the two batch slots the last
+    run ended on. With batch_size 4, one gs_schedule of 4k plain pods runs k batches, and the current slot flips each
+    time a speculative batch is kept: when every one is kept the run ends on slot (k - 1) % 2, so the four values of k
+    leave each slot current twice. The library reports no counter of kept speculative batches, so the test cannot see
+    which slot was current: a batch voided for host-side Reserve work (or GS_NO_PIPELINE) leaves the run a slot behind,
+    and the four k then still cover both run lengths' parities without proving that slot 1 was borrowed. After the
+    run: gs_evaluate of 6 pods, a gs_schedule_ext of one extension pod with 5 plain pods behind it, and one more
+    gs_schedule of 4 pods. Every score, code and placement against the oracle on the same event sequence, bit for
+    bit."""
+    from koordinator_amd.engine import Engine
+    c = synth.make_cluster(192, 64, config_id=31)
+    synth.make_numa(c)
+    synth.make_ext(c, gpu_node_pct=50, gpu_pod_pct=50, rsv_node_pct=0, owner_pod_pct=0)
+    gen = c.ext["pod_ext"]
+    is_gpu = gen["gpu_request_mask"] != 0
+    x, plain = int(np.nonzero(is_gpu)[0][0]), np.nonzero(~is_gpu)[0]
+    assert len(plain) >= 31
+    cfg = config.make_config(c.num_nodes, enabled=abi.GS_ENABLE_ALL, batch_size=4)
+    e, o = Engine(cfg), orc.Oracle(cfg)
+    for eng in (e, o):
+        synth.load_into(eng, c)
+        synth.load_ext_into(eng, c, orc.ext_args_default())
+    run1, probe, tail, run2 = plain[:4 * k], plain[16:22], plain[22:27], plain[27:31]
+    mixed = np.concatenate([[x], tail])
+    ext = np.zeros(6, abi.POD_EXT_DTYPE)   # (the pods behind the extension pod are plain whatever the generator drew)
+    ext[0] = gen[x]
+    got, want = [], []
+    for eng, res in ((e, got), (o, want)):
+        res.append(eng.schedule(c.pods[run1], np.arange(4 * k, dtype=np.uint64)))
+        res.append(eng.evaluate(c.pods[probe]))
+        res.append(eng.schedule_ext(c.pods[mixed], ext, 100 + np.arange(6, dtype=np.uint64)))
+        res.append(eng.schedule(c.pods[run2], 200 + np.arange(4, dtype=np.uint64)))
+    for g, w in zip(got[1], want[1]):   # scores, codes, per-plugin scores
+        assert np.array_equal(g, w)
+    # Reserve flags: the oracle's schedule reports the affinity hint too, its schedule_ext the NUMA / cpuset bits only
+    # (as in the tests above)
+    reserve = abi.GS_PLACED_NUMA | abi.GS_PLACED_CPUSET
+    hint = 0xF << abi.GS_PLACED_AFFINITY_SHIFT
+    for g, w, mask in ((got[0], want[0], reserve | hint), (got[2][0], want[2][0], reserve),
+                       (got[3], want[3], reserve | hint)):
+        placed = w["node"] >= 0
+        for f in ("node", "feasible"):
+            assert np.array_equal(g[f], w[f]), f
+        assert np.array_equal(g["score"][placed], w["score"][placed])
+        assert np.array_equal(g["ties"][placed], w["ties"][placed])
+        assert np.array_equal(g["flags"] & mask, w["flags"] & mask), "Reserve flags differ"
+    assert got[2][1].tobytes() == want[2][1].tobytes()   # the extension pod's Reserve results (zero for the plain pods)
+    assert want[2][1]["gpu_count"][0] > 0 and (want[0]["node"] >= 0).all()
+    assert e.mirror_check() == 0
+
+
 @pytest.mark.parametrize("n,numa", [(2, False), (3, True)], ids=["2ranks", "3ranks-numa"])
 def test_c5_on_several_ranks_score_rows(n, numa):
     """Reservation + DeviceShare pods on several ranks (threads over the in-process device transport, the default
