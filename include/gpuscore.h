@@ -443,6 +443,49 @@ int gs_schedule_submit(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const ui
  * (GS_ESTATE), leaving the context as a failed gs_schedule would. */
 int gs_schedule_wait(gs_ctx* ctx, uint64_t ticket);
 
+/* ---- FitError diagnosis ----
+ * What [upstream] scheduleOne returns for a pod no node can hold: a framework.FitError (framework/types.go) whose
+ * Diagnosis.NodeToStatusMap (schedule_one.go findNodesThatFitPod) holds the Filter status of every node.
+ * gs_schedule_diag reports that map summed per reason, which is all FitError.Error() prints:
+ * "0/5000 nodes are available: 1200 Insufficient cpu, 3800 node(s) cpu usage exceed threshold."
+ * One counter per reason text a Filter status can carry. RunFilterPlugins stops at the first failing plugin, in the
+ * order gs_reason_string applies (NodeResourcesFit, LoadAwareScheduling, NodeNUMAResource): a node Fit fails counts
+ * once under each of Fit's reasons (pods, cpu, memory, ephemeral-storage, each failing scalar slot), else once under
+ * LoadAware's reason (cpu / memory, plain / aggregated), else once under NodeNUMAResource's. */
+enum gs_fit_reason {
+  GS_FR_FIT_PODS = 0, GS_FR_FIT_CPU = 1, GS_FR_FIT_MEMORY = 2, GS_FR_FIT_EPHEMERAL = 3,
+  GS_FR_FIT_SCALAR0 = 4,        /* ..7: resource slots 3..6, counted per slot */
+  GS_FR_LA_CPU = 8, GS_FR_LA_MEMORY = 9, GS_FR_LA_CPU_AGG = 10, GS_FR_LA_MEMORY_AGG = 11,
+  GS_FR_NUMA0 = 11,             /* gs_numa_reason r (1..11) at GS_FR_NUMA0 + r, i.e. 12..22 */
+  GS_NUM_FIT_REASONS = 23
+};
+typedef struct gs_fit_diagnosis {
+  uint32_t valid;               /* 1: this pod was a FitError and the fields below are filled; else all 0 */
+  uint32_t num_all_nodes;       /* FitError.NumAllNodes */
+  uint32_t failed_nodes;        /* nodes with a non-success status (= num_all_nodes for a FitError) */
+  uint32_t unresolvable_nodes;  /* nodes whose status is UnschedulableAndUnresolvable (gs_reason_string's code 2):
+                                   the nodes preemption would skip */
+  uint32_t reasons[24];         /* [gs_fit_reason] node counts; [23] reserved 0 */
+} gs_fit_diagnosis;
+/* gs_schedule / gs_schedule_submit with the diagnosis: out[] is exactly what the plain call writes; for every pod
+ * with out[i].node == -1, diag[i] is the histogram over all num_nodes nodes of the status the Filter chain gives the
+ * node at pod i's turn (after every earlier placement of the same call and batch, before any later one); every other
+ * diag[i] is zeroed. The per-node map itself is not returned. Scope: one rank, no node sampling
+ * (gs_config.sample_nodes = 0), no extension pods; with several ranks or node sampling both calls return
+ * GS_EUNSUPPORTED before anything is scheduled. diag must stay valid like out. The plain calls run no diagnosis
+ * work at all. */
+int gs_schedule_diag(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                     gs_fit_diagnosis* diag);
+int gs_schedule_submit_diag(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                            gs_fit_diagnosis* diag, uint64_t* ticket);   /* waited on with gs_schedule_wait */
+/* [upstream] framework/types.go FitError.Error() of a diagnosis: "0/<num_all_nodes> nodes are available: ", the
+ * entries "<count> <reason text>" of the non-zero counters (counts of reasons that share a text merged; texts and
+ * scalar_names as gs_reason_string's), sorted as whole strings bytewise (Go's sort.Strings: "10 Insufficient cpu"
+ * before "2 Too many pods") and joined by ", ", then ".". types.go is not part of the reference tree: parity is
+ * unpinned. Written to buf NUL-terminated, truncated to len; returns the untruncated length (valid == 0: the empty
+ * string, 0), GS_EINVAL for a NULL diagnosis. */
+int gs_fit_error_string(const gs_fit_diagnosis* diag, const char* const* scalar_names, char* buf, size_t len);
+
 /* ---- NodeNUMAResource state ---- */
 /* Register a CPUTopology; returns its id in *id (identical topologies may share one id). */
 int gs_topology_register(gs_ctx* ctx, const gs_cpu_topology* topo, int32_t* id);

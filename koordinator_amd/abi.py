@@ -58,6 +58,26 @@ NUMA_REASONS = ["OK", "InvalidRequestedCPUs", "InvalidAmplificationRatio", "Avai
                 "InsufficientAmplifiedCPU", "InvalidCPUTopology", "CPUBindPolicyConflict", "SMTAlignment",
                 "AllocateFailed", "MissingNUMAResources", "NUMATopologyAffinity", "AdmitAllocateFailed"]
 GS_PLACED_NUMA, GS_PLACED_CPUSET, GS_PLACED_AFFINITY_SHIFT = 0x2, 0x4, 8
+# gs_fit_reason: the counters of a gs_fit_diagnosis (NodeNUMAResource reason r at GS_FR_NUMA0 + r)
+GS_FR_FIT_PODS, GS_FR_FIT_CPU, GS_FR_FIT_MEMORY, GS_FR_FIT_EPHEMERAL, GS_FR_FIT_SCALAR0 = 0, 1, 2, 3, 4
+GS_FR_LA_CPU, GS_FR_LA_MEMORY, GS_FR_LA_CPU_AGG, GS_FR_LA_MEMORY_AGG, GS_FR_NUMA0 = 8, 9, 10, 11, 11
+GS_NUM_FIT_REASONS = 23
+
+
+def fit_error_message(diag, scalar_names=None) -> str:
+    """[upstream] FitError.Error() of one gs_fit_diagnosis (a FIT_DIAGNOSIS_DTYPE record or a GsFitDiagnosis):
+    gs_fit_error_string. scalar_names: the names of resource slots 3..6 (None: the defaults). '' when not valid."""
+    d = diag if isinstance(diag, GsFitDiagnosis) else GsFitDiagnosis.from_buffer_copy(
+        np.ascontiguousarray(np.atleast_1d(diag), FIT_DIAGNOSIS_DTYPE)[:1].tobytes())
+    names = None
+    if scalar_names is not None:
+        names = (C.c_char_p * 4)(*[n.encode() for n in scalar_names])
+    n = load().gs_fit_error_string(C.byref(d), names, None, 0)
+    if n < 0:
+        raise ValueError(f"gs_fit_error_string: {n}")
+    buf = C.create_string_buffer(n + 1)
+    load().gs_fit_error_string(C.byref(d), names, buf, len(buf))
+    return buf.value.decode()
 
 GS_FAIL_FIT_PODS, GS_FAIL_FIT_CPU, GS_FAIL_FIT_MEMORY = 0x01, 0x02, 0x04
 GS_FAIL_FIT_EPHEMERAL, GS_FAIL_FIT_SCALAR, GS_FAIL_LOADAWARE = 0x08, 0x10, 0x20
@@ -176,6 +196,11 @@ class GsPlacement(C.Structure):
     _fields_ = [("node", i32), ("feasible", u32), ("score", i64), ("ties", u32), ("flags", u32)]
 
 
+class GsFitDiagnosis(C.Structure):
+    _fields_ = [("valid", u32), ("num_all_nodes", u32), ("failed_nodes", u32), ("unresolvable_nodes", u32),
+                ("reasons", u32 * 24)]
+
+
 class GsStats(C.Structure):
     _fields_ = [
         ("batches", u64), ("pods", u64), ("cuts", u64), ("slowpath_pods", u64),
@@ -292,6 +317,7 @@ NODE_DTYPE = np.dtype(GsNode)
 METRIC_DTYPE = np.dtype(GsNodeMetric)
 POD_METRIC_DTYPE = np.dtype(GsPodMetric)
 PLACEMENT_DTYPE = np.dtype(GsPlacement)
+FIT_DIAGNOSIS_DTYPE = np.dtype(GsFitDiagnosis)
 TOPOLOGY_DTYPE = np.dtype(GsCpuTopology)
 NODE_NUMA_DTYPE = np.dtype(GsNodeNuma)
 POD_ALLOCATION_DTYPE = np.dtype(GsPodAllocation)
@@ -335,6 +361,9 @@ SIGNATURES = {
     "gs_schedule": (C.c_int, [P, P, u32, P, P]),
     "gs_schedule_submit": (C.c_int, [P, P, u32, P, P, C.POINTER(u64)]),
     "gs_schedule_wait": (C.c_int, [P, u64]),
+    "gs_schedule_diag": (C.c_int, [P, P, u32, P, P, P]),
+    "gs_schedule_submit_diag": (C.c_int, [P, P, u32, P, P, P, C.POINTER(u64)]),
+    "gs_fit_error_string": (C.c_int, [P, P, C.c_char_p, C.c_size_t]),
     "gs_comm_unique_id": (C.c_int, [P]),
     "gs_comm_init_rccl": (C.c_int, [P, P, C.c_int, C.c_int]),
     "gs_comm_init_callback": (C.c_int, [P, C.c_int, C.c_int, ALLGATHER_FN, P]),

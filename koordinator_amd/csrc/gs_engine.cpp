@@ -32,6 +32,7 @@
 #include "gs_kernels.h"
 #include "gs_numa_host.h"
 #include "gs_owned.h"
+#include "gs_reasons.h"
 
 using namespace gs;
 
@@ -98,6 +99,19 @@ struct Slot {
   // the verdict on the batch's exchange tags (score rows: the slot's own, written by unpack_scores_kernel; levels:
   // merge_levels_kernel's, one block for both slots; one rank: none)
   int32_t* d_xerr = nullptr;
+  // FitError diagnosis (gs_schedule_diag; allocated by the context's first such run, alloc_diag)
+  bool diag_on = false;             // the slot's batch runs the wide pass behind its commit
+  Event ev_dg;                      // the wide pass's end (a readback on st_rb waits for it)
+  DevBuf<uint32_t> d_diag;          // [MAX_BATCH][DIAG_WORDS]: the wide pass's counters, read back with the placements
+  PinnedBuf<uint32_t> h_diag;
+  // the landed pass of the slot's batch (diag_landed): one staged block (row versions | their slab indices | pod
+  // vectors | version indices), the slab the versions are scattered into, and the pass's counters
+  PinnedBuf<uint8_t> h_dgl;
+  DevBuf<uint8_t> d_dgl;
+  DevBuf<int64_t> dgl_i64;
+  DevBuf<int32_t> dgl_i32;
+  DevBuf<uint32_t> d_ldiag;
+  PinnedBuf<uint32_t> h_ldiag;
 };
 
 }  // namespace
@@ -108,6 +122,7 @@ struct AsyncRun {
   std::vector<gs_pod> pods;
   std::vector<uint64_t> seq;
   gs_placement* out = nullptr;
+  gs_fit_diagnosis* diag = nullptr;   // gs_schedule_submit_diag
   uint64_t ticket = 0;
   int rc = 1;   // 1: not complete
   std::string err;
@@ -166,6 +181,7 @@ struct gs_ctx {
   Stream st2;                               // side stream: eval_kernel beside eval_numa_kernel
   Stream st_ev;                             // eval passes: a batch's eval runs beside the previous batch's commit
   Stream st_rb;                             // a batch's placement readback, off the stream the next batch runs on
+  Stream st_dg;                             // FitError diagnosis: the landed pass, off the commit stream (alloc_diag)
   Event ev_fork, ev_join;
   std::vector<Event> x_ev;                  // RCCL all-gather start / end events not yet accounted (exchange_ms)
   int x_pending = 0;
@@ -250,6 +266,9 @@ struct gs_ctx {
   bool host_timing = false;
   double ht_wait = 0, ht_apply = 0, ht_stage = 0, ht_launch = 0, ht_max_busy = 0;
   uint64_t ht_batches = 0, ht_busy_hist[8] = {};
+  // ... and of the FitError diagnosis: deriving the landed-row versions, the landed pass (upload to counters, waited for)
+  double hd_derive = 0, hd_landed = 0;
+  uint64_t hd_batches = 0, hd_versions = 0, hd_pods = 0;
   // ... and of gs_schedule_ext: per extension pod (records, flushes, the device chain up to the host's wake-up, the
   // Reserves) and per plain run (the whole gs_schedule call)
   double hx_prep = 0, hx_flush = 0, hx_gpu = 0, hx_reserve = 0, hx_plain = 0;
@@ -1315,12 +1334,85 @@ CommitArgs commit_args(gs_ctx* c, const Slot& s, int b) {
   return a;
 }
 
+// ---- FitError diagnosis (gs_schedule_diag; kernels: gs_fit_diag.hip) ----
+constexpr size_t DIAG_BYTES = sizeof(uint32_t) * MAX_BATCH * DIAG_WORDS;
+// the landed pass's staged block at its largest: DIAG_VERSIONS rows and indices, MAX_BATCH pod vectors, the index table
+constexpr size_t DGL_BYTES = (size_t)DIAG_VERSIONS * (ROW_WORDS * 8 + 4) + 8 + sizeof(PodVec) * MAX_BATCH +
+                             2 * (size_t)MAX_BATCH * MAX_BATCH;
+
+// the buffers and the stream of the diagnosis, on the context's first run that asks for one
+int alloc_diag(gs_ctx* c) {
+  if (c->st_dg) return GS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  for (Slot& s : c->slot) {
+    HIP_TRY(c, s.ev_dg.create(hipEventDisableTiming));
+    HIP_TRY(c, s.d_diag.alloc(DIAG_BYTES));
+    HIP_TRY(c, s.h_diag.alloc(DIAG_BYTES));
+    HIP_TRY(c, s.h_dgl.alloc(DGL_BYTES));
+    HIP_TRY(c, s.d_dgl.alloc(DGL_BYTES));
+    HIP_TRY(c, s.dgl_i64.alloc((size_t)NUM_I64_COLS * DIAG_VERSIONS * 8));
+    HIP_TRY(c, s.dgl_i32.alloc((size_t)NUM_I32_COLS * DIAG_VERSIONS * 4));
+    HIP_TRY(c, s.d_ldiag.alloc(DIAG_BYTES));
+    HIP_TRY(c, s.h_ldiag.alloc(DIAG_BYTES));
+  }
+  HIP_TRY(c, c->st_dg.create(hipStreamNonBlocking));
+  return GS_OK;
+}
+
+DiagArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
+  DiagArgs a{};
+  a.m = c->mv;
+  a.pods = s.d_pods.get();
+  a.pf = c->pf;
+  a.N = c->N;
+  a.npods = b;
+  a.committed = s.d_committed.get();
+  a.out = s.d_out;
+  a.diag = s.d_diag.get();
+  a.numa_idx = c->d_numa_idx.get();   // (one rank: the list covers every node)
+  a.numa_n = c->numa_on ? c->numa_n : 0;
+  return a;
+}
+
+// The landed pass of a batch (blocking; off the commit stream): nv row versions staged at the head of s.h_dgl are
+// scattered into the slot's slab with their LoadAware verdicts at `now`, pod f (fpods[f]) is evaluated on versions
+// vidx[f * nL ..], and the nF pods' counters arrive in s.h_ldiag.
+int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL) {
+  const int nF = (int)fpods.size();
+  const size_t off_idx = (size_t)nv * ROW_WORDS * 8;
+  const size_t off_pods = (off_idx + (size_t)nv * 4 + 7) & ~(size_t)7;
+  const size_t off_vidx = off_pods + sizeof(PodVec) * nF;
+  const size_t total = off_vidx + 2 * (size_t)nF * nL;
+  if (nv > DIAG_VERSIONS || total > DGL_BYTES) return fail(c, GS_ESTATE, "FitError diagnosis: landed-row versions overflow");
+  uint8_t* h = s.h_dgl.get();
+  uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + off_idx);
+  for (int v = 0; v < nv; ++v) h_idx[v] = (uint32_t)v;
+  std::memcpy(h + off_pods, fpods.data(), sizeof(PodVec) * nF);
+  std::memcpy(h + off_vidx, vidx.data(), 2 * (size_t)nF * nL);
+  const hipStream_t st = c->st_dg.get();
+  uint8_t* d = s.d_dgl.get();
+  const MirrorView slab{s.dgl_i64.get(), s.dgl_i32.get(), (uint32_t)DIAG_VERSIONS};
+  const gs_loadaware_args& la = c->cfg.loadaware;
+  const ScatterPrep sp{c->now, la.filter_expired_node_metrics, la.has_node_metric_expiration,
+                       la.has_node_metric_expiration ? la.node_metric_expiration_seconds * 1000000000LL : 0};
+  HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, launch_scatter_rows(slab, reinterpret_cast<const uint32_t*>(d + off_idx), reinterpret_cast<const int64_t*>(d),
+                                 (uint32_t)nv, st, &sp));
+  HIP_TRY(c, launch_fit_diag_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
+                                    reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(), st));
+  HIP_TRY(c, hipMemcpyAsync(s.h_ldiag.get(), s.d_ldiag.get(), sizeof(uint32_t) * DIAG_WORDS * nF, hipMemcpyDeviceToHost, st));
+  Where w_(c, "diag_landed: the landed pass");
+  HIP_TRY(c, host_wait_stream(st));
+  return GS_OK;
+}
+
 // Enqueue one device pass over pods [0, b) of slot s's staged batch, and its read-back; no host wait.
 // The eval pass runs on st_ev, the rest on st. before != nullptr: a speculative pass behind slot `before`'s batch of
 // prev_b pods (prev: its committed words, prev_out: its placements): its eval pass runs beside that batch's commit, on
 // the mirror as it was before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel);
 // its commit kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
-int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0) {
+// diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements.
+int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0, bool diag = false) {
   const int32_t* prev = before ? before->d_committed.get() : nullptr;
   const PlacementDev* prev_out = before ? before->d_out : nullptr;
   const hipStream_t st = c->st.get(), st_ev = c->st_ev.get();
@@ -1452,11 +1544,22 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
   HIP_TRY(c, launch_commit(a, st));
   if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
   if (rb != st) HIP_TRY(c, hipStreamWaitEvent(rb, s.ev[4].get(), 0));
+  s.diag_on = diag;
+  if (diag) {   // behind the commit's write-back, before the next batch's fix-up and commit (stream order)
+    HIP_TRY(c, hipMemsetAsync(s.d_diag.get(), 0, DIAG_BYTES, st));
+    HIP_TRY(c, launch_fit_diag(diag_args(c, s, b), st));
+    if (rb != st) {
+      HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
+      HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
+    }
+  }
   // Two copies, not one over the adjacent committed words and placements: with one merged copy, 4 processes sharing the
   // GPU (the C4 rehearsal) stalled for 10-100 s at a time, every rank's commit and next eval pass pending;
   // for a direct batch the merged form measured within noise
   HIP_TRY(c, hipMemcpyAsync(s.h_committed.get(), s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
   HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
+  if (diag)
+    HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * b, hipMemcpyDeviceToHost, rb));
   HIP_TRY(c, hipEventRecord(s.ev[5].get(), rb));
   return GS_OK;
 }
@@ -1525,6 +1628,13 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     }
     if (M < 0) {
       s.h_out[0] = PlacementDev{-1, (uint32_t)F, 0, 0, GS_PLACED_SLOWPATH, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+      if (s.diag_on) {   // a FitError the host found: nothing landed in the pass, every node from the mirror
+        DiagArgs da = diag_args(c, s, b);
+        da.force0 = 1;
+        HIP_TRY(c, launch_fit_diag(da, st));
+        HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, host_wait_stream(st));
+      }
       *committed_out = 1;
       return GS_OK;
     }
@@ -1559,12 +1669,16 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     HIP_TRY(c, hipEventRecord(s.ev[3].get(), st));
     HIP_TRY(c, launch_commit(a, st));
     HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
+    if (s.diag_on) HIP_TRY(c, launch_fit_diag(diag_args(c, s, b), st));   // (the first pass committed nothing: counters 0)
     HIP_TRY(c, hipMemcpyAsync(h_committed, s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
     c->stats.commit_ms += ev_ms(s.ev[3].get(), s.ev[4].get());
     committed = h_committed[0];
     if (committed < 1) return fail(c, GS_ESTATE, "forced commit made no progress");
     HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * committed, hipMemcpyDeviceToHost, st));
+    if (s.diag_on)
+      HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * committed,
+                                hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
   }
   flush_exchange_times(c);
@@ -2293,6 +2407,13 @@ void report_host_timing(const gs_ctx* c) {
             c->hx_prep / n, c->hx_flush / n, c->hx_gpu / n, c->hx_reserve / n, (unsigned long long)c->hx_runs,
             c->hx_runs ? c->hx_plain / (double)c->hx_runs : 0.0);
   }
+  if (c->host_timing && c->hd_batches) {
+    const double n = (double)c->hd_batches;
+    fprintf(stderr, "gpuscore FitError diagnosis, host per batch with such a pod (us, %llu batches, %llu pods, %llu "
+            "landed-row versions): deriving the versions %.1f | landed pass, upload to counters %.1f\n",
+            (unsigned long long)c->hd_batches, (unsigned long long)c->hd_pods, (unsigned long long)c->hd_versions,
+            c->hd_derive / n, c->hd_landed / n);
+  }
 }
 
 // GS_COMMIT_STAMPS=1: the commit kernel's phase cycle sums, on stderr
@@ -2411,7 +2532,7 @@ int gs_destroy(gs_ctx* c) {
   report_commit_stamps(c);
   if (c->comm) ncclCommDestroy(c->comm);
   // readbacks into the pinned buffers and the side stream's eval pass may still be in flight
-  for (const Stream* s : {&c->st, &c->st_ev, &c->st_rb, &c->st2})
+  for (const Stream* s : {&c->st, &c->st_ev, &c->st_rb, &c->st2, &c->st_dg})
     if (*s) (void)host_wait_stream(s->get());
   delete c;
   return GS_OK;
@@ -2656,6 +2777,7 @@ struct PodRun {
   gs_placement* out = nullptr;
   uint32_t n = 0;
   void* tag = nullptr;
+  gs_fit_diagnosis* diag = nullptr;   // gs_schedule_diag: the FitError diagnosis of each pod (else none is computed)
 };
 
 // Several ranks: whether the next run is already known (gs_schedule_submit) is a matter of each rank's timing. The
@@ -2691,8 +2813,40 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     (void)host_wait_stream(c->st_ev.get());
     (void)host_wait_stream(c->st_rb.get());   // a voided or in-flight batch's readback into the pinned buffers
   };
+  // dg != nullptr: the batch's FitError diagnoses into dg[0..n). wide: the wide pass's counters of the batch ([pod]
+  // [DIAG_WORDS]: every node the batch did not land on); the landed nodes are added here: walking the placements in
+  // queue order, the host state of every node at a pod with no node is its state at that pod's turn, so the
+  // device-format rows of the batch's landed nodes are derived there (derive_row / derive_row_numa, the two
+  // gs_debug_mirror_check holds to the device's rows) — a row changes only at a landing, so each version is derived
+  // once and the pod gets an index per landed node — and evaluated by the landed pass on slot sl's buffers.
+  std::vector<uint32_t> dg_nodes;
+  std::vector<uint16_t> dg_cur, dg_vidx;
+  std::vector<uint8_t> dg_stale;
+  std::vector<PodVec> dg_pods;
+  std::vector<int> dg_k;
   auto apply_batch = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
-                         bool special) -> int {
+                         bool special, gs_fit_diagnosis* dg = nullptr, const uint32_t* wide = nullptr,
+                         Slot* sl = nullptr) -> int {
+    int nfit = 0, nv = 0;
+    if (dg) {
+      std::memset(dg, 0, sizeof(gs_fit_diagnosis) * n);
+      dg_nodes.clear();
+      for (int k = 0; k < n; ++k) {
+        if (hout[k].node < 0) ++nfit;
+        else if (std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)hout[k].node) == dg_nodes.end())
+          dg_nodes.push_back((uint32_t)hout[k].node);
+      }
+      if (!nfit) dg = nullptr;
+    }
+    const int nL = dg ? (int)dg_nodes.size() : 0;
+    if (dg) {
+      dg_cur.assign(nL, 0);
+      dg_stale.assign(nL, 1);
+      dg_vidx.clear();
+      dg_pods.clear();
+      dg_k.clear();
+    }
+    double t_derive = 0;
     for (int k = 0; k < n; ++k) {
       const PlacementDev& pd = hout[k];
       gs_placement& o = outp[k];
@@ -2702,8 +2856,50 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       o.ties = pd.node >= 0 ? pd.ties : 0;
       o.flags = pd.flags & ~PL_INTERNAL_FLAGS;
       if (pd.flags & GS_PLACED_SLOWPATH) c->stats.slowpath_pods += 1;   // resolved from its whole score row
+      if (dg && pd.node < 0) {
+        const int64_t t0 = c->host_timing ? mono_ns() : 0;
+        for (int j = 0; j < nL; ++j) {
+          if (dg_stale[j]) {
+            if (nv >= DIAG_VERSIONS) return fail(c, GS_ESTATE, "FitError diagnosis: landed-row versions overflow");
+            int64_t* row = reinterpret_cast<int64_t*>(sl->h_dgl.get()) + (size_t)nv * ROW_WORDS;
+            derive_row(c, dg_nodes[j], row);
+            derive_row_numa(c, dg_nodes[j], row);
+            dg_cur[j] = (uint16_t)nv++;
+            dg_stale[j] = 0;
+          }
+          dg_vidx.push_back(dg_cur[j]);
+        }
+        dg_pods.push_back(hpods[k]);
+        dg_k.push_back(k);
+        if (c->host_timing) t_derive += (double)(mono_ns() - t0) * 1e-3;
+      }
       if (int rc = numa_reserve(c, pods[k], hpods[k], pd)) return rc;
       apply_placement(c, pods[k], pd.node, special);
+      if (dg && pd.node >= 0)
+        dg_stale[std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)pd.node) - dg_nodes.begin()] = 1;
+    }
+    if (!dg) return GS_OK;
+    const int64_t t1 = c->host_timing ? mono_ns() : 0;
+    if (nL)
+      if (int rc = diag_landed(c, *sl, nv, dg_pods, dg_vidx, nL)) return rc;
+    const uint32_t* landed = sl->h_ldiag.get();
+    for (size_t f = 0; f < dg_k.size(); ++f) {
+      const int k = dg_k[f];
+      gs_fit_diagnosis& d = dg[k];
+      d.valid = 1;
+      d.num_all_nodes = c->N;
+      for (int r = 0; r < GS_NUM_FIT_REASONS; ++r) {
+        d.reasons[r] = wide[(size_t)k * DIAG_WORDS + r] + (nL ? landed[f * DIAG_WORDS + r] : 0u);
+        if (fit_reason_status(r) == 2) d.unresolvable_nodes += d.reasons[r];
+      }
+      d.failed_nodes = wide[(size_t)k * DIAG_WORDS + DIAG_FAILED] + (nL ? landed[f * DIAG_WORDS + DIAG_FAILED] : 0u);
+    }
+    if (c->host_timing) {
+      c->hd_derive += t_derive;
+      c->hd_landed += (double)(mono_ns() - t1) * 1e-3;
+      c->hd_batches += 1;
+      c->hd_versions += nv;
+      c->hd_pods += dg_k.size();
     }
     return GS_OK;
   };
@@ -2716,13 +2912,17 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     gs_placement* out = nullptr;
     int n = 0;
     bool active = false;
+    gs_fit_diagnosis* diag = nullptr;
+    Slot* slot = nullptr;   // the slot the batch ran on (its landed-pass buffers)
   } pend;
   std::vector<PlacementDev> pend_out;
   std::vector<PodVec> pend_pods;
+  std::vector<uint32_t> pend_wide;
   auto apply_pending = [&]() -> int {
     if (!pend.active) return GS_OK;
     pend.active = false;
-    return apply_batch(pend.pods, pend.out, pend.n, pend_out.data(), pend_pods.data(), false);
+    return apply_batch(pend.pods, pend.out, pend.n, pend_out.data(), pend_pods.data(), false, pend.diag,
+                       pend_wide.data(), pend.slot);
   };
   auto body = [&]() -> int {
     int rc = GS_OK;
@@ -2751,20 +2951,21 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         cur_b = batch_len(c, pods, i, run.n, &cur_special);
         // (a cpuset pod whose node is outside the device cpuset scope ends the batch inside the commit kernel)
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr))) return rc;
       }
       // the batch after this one: in this run, or the first of the next run
       const gs_pod* np = nullptr;
       const uint64_t* ns = nullptr;
       uint32_t nj = 0, nn = 0;
       const uint32_t j = i + cur_b;
+      bool ndiag = run.diag != nullptr;   // whether the batch after this one is diagnosed (its own run's choice)
       if (j < run.n) {
         np = pods; ns = run.seq; nj = j; nn = run.n;
       } else {
         if (!have_nxt) have_nxt = next_run(&nxt);
         bool use = have_nxt && nxt.n;
         if (c->nranks > 1 && (rc = agree_next_run(c, &use))) { drain(); return rc; }
-        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; }
+        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; }
       }
       bool spec = false;
       int nb = 0;
@@ -2781,7 +2982,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         if (!sf && !uid_overlap(pods + i, cur_b, np + nj, nb)) {
           rc = stage_batch(c, ahead, np, ns, nj, nb, true);
           const auto t_b = hclk::now();
-          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b);
+          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag);
           if (c->host_timing) {
             const double st = std::chrono::duration<double, std::micro>(t_b - t_a).count();
             const double la = std::chrono::duration<double, std::micro>(hclk::now() - t_b).count();
@@ -2804,7 +3005,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         drain();
         if ((rc = apply_pending())) return rc;
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr))) return rc;
         inflight = true;
         spec_ok = false;
         continue;
@@ -2822,7 +3023,11 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         pend.out = run.out + i;
         pend.n = committed;
         pend.active = true;
-      } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special))) {
+        pend.diag = run.diag ? run.diag + i : nullptr;
+        pend.slot = &cur;
+        if (run.diag) pend_wide.assign(cur.h_diag.get(), cur.h_diag.get() + (size_t)DIAG_WORDS * committed);
+      } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special,
+                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur))) {
         if (spec) drain();
         return rc;
       }
@@ -2890,6 +3095,7 @@ void async_worker(gs_ctx* c) {
       p.pods = r->pods.data();
       p.seq = r->seq.data();
       p.out = r->out;
+      p.diag = r->diag;
       p.n = (uint32_t)r->pods.size();
       p.tag = r.get();
       return p;
@@ -2947,9 +3153,17 @@ void async_stop(gs_ctx* c) {
 
 }  // extern "C++"
 
-int gs_schedule(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out) {
-  if (!c || (npods && (!pods || !out))) return GS_EINVAL;
-  quiesce(c);
+namespace {
+// the scope of the FitError diagnosis: one rank, every node checked (the wide pass reads the whole mirror of one
+// rank's commit; under node sampling the reference's map holds only the nodes of the rotation window)
+int diag_supported(gs_ctx* c) {
+  if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "FitError diagnosis: several ranks are not supported");
+  if (c->window_k) return fail(c, GS_EUNSUPPORTED, "FitError diagnosis: node sampling is not supported");
+  return GS_OK;
+}
+
+int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                 gs_fit_diagnosis* diag) {
   int rc = ready(c);
   if (rc) return rc;
   for (uint32_t i = 0; i < npods; ++i)
@@ -2959,12 +3173,13 @@ int gs_schedule(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* s
   run.seq = seq;
   run.out = out;
   run.n = npods;
+  run.diag = diag;
   return schedule_stream(c, run, [](PodRun*) { return false; }, [](const PodRun&, int) {});
 }
 
-int gs_schedule_submit(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                       uint64_t* ticket) {
-  if (!c || !ticket || (npods && (!pods || !out))) return GS_EINVAL;
+// gs_schedule_submit: the run copied and queued for the worker
+int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+               gs_fit_diagnosis* diag, uint64_t* ticket) {
   auto r = std::make_shared<AsyncRun>();
   // checks that write nothing (the worker may be running): on an error, wait for it, then report
   if (c->n_valid != c->N) {
@@ -2983,6 +3198,7 @@ int gs_schedule_submit(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint
   r->seq.resize(npods);
   for (uint32_t i = 0; i < npods; ++i) r->seq[i] = seq ? seq[i] : (uint64_t)i;
   r->out = out;
+  r->diag = diag;
   if (!c->aq) {
     c->aq = std::make_unique<AsyncQueue>();
     c->aq->th = std::thread(async_worker, c);
@@ -2996,6 +3212,40 @@ int gs_schedule_submit(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint
   c->aq->cv_work.notify_all();
   *ticket = r->ticket;
   return GS_OK;
+}
+}  // namespace
+
+int gs_schedule(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out) {
+  if (!c || (npods && (!pods || !out))) return GS_EINVAL;
+  quiesce(c);
+  return schedule_run(c, pods, npods, seq, out, nullptr);
+}
+
+int gs_schedule_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                     gs_fit_diagnosis* diag) {
+  if (!c || (npods && (!pods || !out || !diag))) return GS_EINVAL;
+  quiesce(c);
+  if (int rc = diag_supported(c)) return rc;
+  if (int rc = alloc_diag(c)) return rc;
+  return schedule_run(c, pods, npods, seq, out, npods ? diag : nullptr);
+}
+
+int gs_schedule_submit(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                       uint64_t* ticket) {
+  if (!c || !ticket || (npods && (!pods || !out))) return GS_EINVAL;
+  return submit_run(c, pods, npods, seq, out, nullptr, ticket);
+}
+
+int gs_schedule_submit_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                            gs_fit_diagnosis* diag, uint64_t* ticket) {
+  if (!c || !ticket || (npods && (!pods || !out || !diag))) return GS_EINVAL;
+  // (the rank count and the sampling window are fixed before any submission: read beside the worker)
+  if (c->nranks > 1 || c->window_k || !c->st_dg) {
+    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
+    if (int rc = diag_supported(c)) return rc;
+    if (int rc = alloc_diag(c)) return rc;
+  }
+  return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket);
 }
 
 int gs_schedule_wait(gs_ctx* c, uint64_t ticket) {

@@ -229,6 +229,33 @@ struct ScatterPrep {   // node_prep_kernel's arguments, fused into the scatter
 };
 hipError_t launch_scatter_rows(const MirrorView& m, const uint32_t* idx, const int64_t* rows, uint32_t nrows,
                                hipStream_t st, const ScatterPrep* prep = nullptr);
+// ---- FitError diagnosis (gs_fit_diag.hip; gs_schedule_diag) ----
+// Per pod of a batch DIAG_WORDS counters: [gs_fit_reason] node counts, then at DIAG_FAILED the nodes with any failure.
+constexpr int DIAG_WORDS = 24, DIAG_FAILED = 23;
+constexpr int DIAG_VERSIONS = 2 * MAX_BATCH;   // landed-row versions per batch: distinct landed nodes + landings
+struct DiagArgs {
+  MirrorView m;
+  const PodVec* pods;        // the batch's pod vectors
+  Profile pf;
+  uint32_t N;                // nodes (padding rows are never counted)
+  int npods;                 // pods of the pass
+  const int32_t* committed;  // the pass's committed words ([0]: pods committed; a voided pass: -1)
+  const PlacementDev* out;   // its placements
+  uint32_t* diag;            // [pod][DIAG_WORDS], added to
+  int force0;                // the host found pod 0 unschedulable (full-row path): pod 0 alone, nothing landed
+  const uint32_t* numa_idx;  // the nodes with a NUMA topology policy (ascending), numa_n of them
+  uint32_t numa_n;
+};
+// The wide pass behind a batch's commit, on its stream: for every committed pod with node < 0, every node < N the
+// batch's committed pods did not land on is evaluated (the mirror holds its state at the pod's turn) and its failure
+// reasons are added to the pod's counters. Does nothing for a voided pass or a batch without such a pod.
+hipError_t launch_fit_diag(const DiagArgs& a, hipStream_t st);
+// The landed rows: block f evaluates pod f (pods[f]) on the nL row versions vidx[f * nL ..] of the slab (host-derived
+// rows of the batch's landed nodes as they were at the pod's turn) and writes the pod's counters to out[f].
+// Reads the slab only.
+hipError_t launch_fit_diag_landed(const MirrorView& slab, const PodVec* pods, const Profile& pf, const uint16_t* vidx,
+                                  int nF, int nL, uint32_t* out, hipStream_t st);
+
 int64_t host_tiebreak_position(uint64_t seed, uint64_t seq, int64_t T);
 // diagnostics (gs_probe.hip): cycles of one pair evaluation as the commit kernel runs it
 hipError_t launch_probe(int mode, const MirrorView& m, const Profile& pf, const PodVec* pods, int npods,

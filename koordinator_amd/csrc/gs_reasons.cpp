@@ -11,9 +11,13 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <map>
 #include <string>
+#include <vector>
 
 #include "../../include/gpuscore.h"
+#include "gs_reasons.h"
 
 namespace {
 
@@ -42,7 +46,36 @@ const NumaReason kNuma[] = {
 const char* const kScalarDefault[4] = {"kubernetes.io/batch-cpu", "kubernetes.io/batch-memory", "kubernetes.io/mid-cpu",
                                        "kubernetes.io/mid-memory"};
 
+// the reason text counter fr (gs_fit_reason) stands for: the one table gs_reason_string and gs_fit_error_string render
+std::string reason_text(int fr, const char* const* scalar_names) {
+  switch (fr) {
+    case GS_FR_FIT_PODS: return "Too many pods";
+    case GS_FR_FIT_CPU: return "Insufficient cpu";
+    case GS_FR_FIT_MEMORY: return "Insufficient memory";
+    case GS_FR_FIT_EPHEMERAL: return "Insufficient ephemeral-storage";
+    default: break;
+  }
+  if (fr >= GS_FR_FIT_SCALAR0 && fr < GS_FR_FIT_SCALAR0 + 4) {
+    const int s = fr - GS_FR_FIT_SCALAR0;
+    return std::string("Insufficient ") + (scalar_names && scalar_names[s] ? scalar_names[s] : kScalarDefault[s]);
+  }
+  if (fr >= GS_FR_LA_CPU && fr <= GS_FR_LA_MEMORY_AGG) {
+    const int d = fr - GS_FR_LA_CPU;   // bit 0: memory, bit 1: the aggregated form
+    return std::string("node(s) ") + ((d & 1) ? "memory" : "cpu") +
+           ((d & 2) ? " aggregated usage exceed threshold" : " usage exceed threshold");
+  }
+  if (fr > GS_FR_NUMA0 && fr < GS_NUM_FIT_REASONS) return kNuma[fr - GS_FR_NUMA0].msg;
+  return "";
+}
+
 }  // namespace
+
+namespace gs {
+int fit_reason_status(int fr) {
+  if (fr < 0 || fr >= GS_NUM_FIT_REASONS) return kSuccess;
+  return fr > GS_FR_NUMA0 ? kNuma[fr - GS_FR_NUMA0].code : kUnschedulable;
+}
+}  // namespace gs
 
 extern "C" int gs_reason_string(uint32_t code, uint32_t scalar_mask, const char* const* scalar_names, char* buf,
                                 size_t len) {
@@ -59,23 +92,18 @@ extern "C" int gs_reason_string(uint32_t code, uint32_t scalar_mask, const char*
   if (fit) {   // the first plugin of the Filter order fails: its reasons, in fitsRequest order
     status = kUnschedulable;
     auto add = [&](const std::string& r) { msg += (msg.empty() ? "" : ", ") + r; };
-    if (code & GS_FAIL_FIT_PODS) add("Too many pods");
-    if (code & GS_FAIL_FIT_CPU) add("Insufficient cpu");
-    if (code & GS_FAIL_FIT_MEMORY) add("Insufficient memory");
-    if (code & GS_FAIL_FIT_EPHEMERAL) add("Insufficient ephemeral-storage");
+    for (int b = 0; b < 4; ++b)   // GS_FAIL_FIT_PODS .. _EPHEMERAL are bits GS_FR_FIT_PODS .. _EPHEMERAL
+      if (code >> b & 1u) add(reason_text(b, scalar_names));
     if (code & GS_FAIL_FIT_SCALAR)
       for (int s = 3; s < 7; ++s)
-        if (scalar_mask >> s & 1u) add(std::string("Insufficient ") + (scalar_names ? scalar_names[s - 3] : kScalarDefault[s - 3]));
+        if (scalar_mask >> s & 1u) add(reason_text(GS_FR_FIT_SCALAR0 + s - 3, scalar_names));
   } else if (code & GS_FAIL_LOADAWARE) {
     status = kUnschedulable;
-    char tmp[96];
-    snprintf(tmp, sizeof(tmp), (code & GS_FAIL_LA_AGGREGATED) ? "node(s) %s aggregated usage exceed threshold"
-                                                              : "node(s) %s usage exceed threshold",
-             (code & GS_FAIL_LA_MEMORY) ? "memory" : "cpu");
-    msg = tmp;
+    msg = reason_text(GS_FR_LA_CPU + ((code & GS_FAIL_LA_MEMORY) ? 1 : 0) + ((code & GS_FAIL_LA_AGGREGATED) ? 2 : 0),
+                      scalar_names);
   } else if (numa) {
     status = kNuma[numa].code;
-    msg = kNuma[numa].msg;
+    msg = reason_text(GS_FR_NUMA0 + (int)numa, scalar_names);
   }
   if (buf && len) {
     const size_t n = msg.size() < len - 1 ? msg.size() : len - 1;
@@ -83,4 +111,31 @@ extern "C" int gs_reason_string(uint32_t code, uint32_t scalar_mask, const char*
     buf[n] = '\0';
   }
   return status;
+}
+
+// [upstream] framework/types.go FitError.Error(): "0/<NumAllNodes> nodes are available: " + the histogram of the
+// NodeToStatusMap's reasons as "<count> <reason>" strings, sorted (sort.Strings: bytewise), joined by ", ", + ".".
+extern "C" int gs_fit_error_string(const gs_fit_diagnosis* d, const char* const* scalar_names, char* buf, size_t len) {
+  if (!d) return GS_EINVAL;
+  std::string msg;
+  if (d->valid) {
+    std::map<std::string, uint64_t> hist;   // counts of reasons that share a text are merged
+    for (int fr = 0; fr < GS_NUM_FIT_REASONS; ++fr) {
+      if (!d->reasons[fr]) continue;
+      const std::string t = reason_text(fr, scalar_names);
+      if (!t.empty()) hist[t] += d->reasons[fr];
+    }
+    std::vector<std::string> entries;
+    for (const auto& e : hist) entries.push_back(std::to_string(e.second) + " " + e.first);
+    std::sort(entries.begin(), entries.end());
+    msg = "0/" + std::to_string(d->num_all_nodes) + " nodes are available: ";
+    for (size_t i = 0; i < entries.size(); ++i) msg += (i ? ", " : "") + entries[i];
+    msg += ".";
+  }
+  if (buf && len) {
+    const size_t n = msg.size() < len - 1 ? msg.size() : len - 1;
+    memcpy(buf, msg.data(), n);
+    buf[n] = '\0';
+  }
+  return (int)msg.size();
 }

@@ -10,6 +10,7 @@
   assign / unassign      podAssignCache.assign / unAssign             (pod_assign_cache.go:53-80)
   evaluate               RunFilterPlugins + RunScorePlugins per node  (load_aware.go:123-171,269-335)
   schedule               scheduleOne loop incl. selectHost + Reserve  ([upstream] schedule_one.go)
+  schedule_diag          ... with the FitError diagnosis of each pod   ([upstream] framework/types.go FitError)
 
 The product path has no CPU fallback: if libgpuscore or a GPU is missing, construction fails.
 """
@@ -148,9 +149,36 @@ class Engine:
         return (t.value, out)
 
     def schedule_wait(self, handle):
-        t, out = handle
+        """The placements of a schedule_submit handle; (placements, diag) of a schedule_submit_diag handle."""
+        t, *res = handle
         self._chk(lib().gs_schedule_wait(self._h, t), "gs_schedule_wait")
-        return out
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def schedule_diag(self, pods, seq=None):
+        """gs_schedule_diag: (placements, diag); diag[i] (abi.FIT_DIAGNOSIS_DTYPE) is the FitError diagnosis of a pod
+        with node -1 (valid = 1), zero otherwise. One rank, no node sampling."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        diag = np.zeros(len(pods), abi.FIT_DIAGNOSIS_DTYPE)
+        self._chk(lib().gs_schedule_diag(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out), abi.ptr(diag)),
+                  "gs_schedule_diag")
+        return out, diag
+
+    def schedule_submit_diag(self, pods, seq=None):
+        """gs_schedule_submit_diag: a handle for schedule_wait, which then returns (placements, diag)."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        diag = np.zeros(len(pods), abi.FIT_DIAGNOSIS_DTYPE)
+        t = C.c_uint64(0)
+        self._chk(lib().gs_schedule_submit_diag(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out),
+                                                abi.ptr(diag), C.byref(t)), "gs_schedule_submit_diag")
+        return (t.value, out, diag)
 
     def pod_event(self, event: int, node_idx, pods):
         """podAssignCache OnAdd / OnUpdate / OnDelete (node_idx -1 = pod.Spec.NodeName == "")."""
