@@ -1,9 +1,9 @@
 // gs_commit_spec.hip — the sequential commit of a batch as a speculative pipeline on one CU (gfx950, one shard).
 //
-// Same contract and results as commit_kernel (gs_kernels.hip): the batch's pods in queue order, each one
-// selectHost over its batch-start score levels and the rows earlier pods of the batch landed on ("dirty" rows,
-// re-scored exactly), then assume + Reserve ([upstream] scheduleOne: selectHost, assume; LoadAware /
-// NodeNUMAResource Reserve).
+// The commit of every batch without node sampling (with it: commit_window_kernel, gs_kernels.hip), with the results
+// of the sequential scheduleOne loop: the batch's pods in queue order, each one selectHost over its batch-start
+// score levels and the rows earlier pods of the batch landed on ("dirty" rows, re-scored exactly), then assume +
+// Reserve ([upstream] scheduleOne: selectHost, assume; LoadAware / NodeNUMAResource Reserve).
 //
 // Why speculative. One wave issues about one instruction per 4-8 cycles, and the exact chain per pod — selection,
 // Reserve of the winner, the winner row's new score for the next pod — is several thousand instructions long. The
@@ -279,7 +279,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
   // header of pod p (lanes 0..7: level j score / count) and the head of its level list (lane i: entry i)
   // (all LEVALL levels: the LevelHdr's first MAXLEV and the LevelExt's rest)
   auto load_hdr = [&](int p, Hdr& o) {
-    const LevelHdr* h = hdr_ptr(a, 0, p);
+    const LevelHdr* h = hdr_ptr(a, p);
     const LevelExt* x = reinterpret_cast<const LevelExt*>(a.xbase + (size_t)a.bmax * LCAP * 4 +
                                                           (size_t)a.bmax * sizeof(LevelHdr)) + p;
     o.nlev = x->nlev;
@@ -287,7 +287,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
     o.next = x->next;
     o.hs = lane < MAXLEV ? h->score[lane] : lane < LEVALL ? x->score[lane - MAXLEV] : -1;
     o.hc = lane < MAXLEV ? h->count[lane] : lane < LEVALL ? x->count[lane - MAXLEV] : 0;
-    o.lh = list_ptr(a, 0, p)[lane];
+    o.lh = list_ptr(a, p)[lane];
     o.tbv = a.tb[(size_t)p * TB_N + (lane & (TB_N - 1))];
   };
   // tiebreak_position(a.seed, seq[p], T) from pod p's records (tbv, lane k: entry k)
@@ -418,12 +418,12 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
       if (nnew == 0 && nold == 0) {
         // no dirty row at M (then level M is listed: M is its clean level): the jp-th listed node of level M
         const int e = off + (int)jp - 1;
-        winner = e < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)lh, e) : list_ptr(a, 0, p)[e];
+        winner = e < 64 ? (uint32_t)__builtin_amdgcn_readlane((int)lh, e) : list_ptr(a, p)[e];
         if (PREP) {   // the ties after it: listed nodes e+1, e+2, ...
           const int nk = (int)min<int64_t>(SP_KW, T - jp + 1);
           const int ek = e + lane;
           const uint32_t fromh = (uint32_t)__shfl((int)lh, ek & 63);
-          if (lane < nk) r.twv = ek < 64 ? fromh : list_ptr(a, 0, p)[ek];
+          if (lane < nk) r.twv = ek < 64 ? fromh : list_ptr(a, p)[ek];
           r.ntw = nk;
         }
         if (ST) { st_acc[24] += e >= 32 ? 1 : 0; st_acc[25] += e >= 64 ? 1 : 0; }
@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         const int e = off + lo + lane;
         const uint32_t fromh = (uint32_t)__shfl((int)lh, e & 63);
         uint32_t x = 0xffffffffu;
-        if (lane < W) x = e < 64 ? fromh : list_ptr(a, 0, p)[e];
+        if (lane < W) x = e < 64 ? fromh : list_ptr(a, p)[e];
         const uint32_t win0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0);
         SPM(46);   // winner (old-nodes path): level segment, window of the list
         bool ow = false;
@@ -471,7 +471,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         const int hi = (int)min<int64_t>(len - 1, jp - 1 + nold);
         const int W = hi - lo + 1;
         if (ST) st_acc[34] += W > 0 ? W : 0;
-        const uint32_t* L = list_ptr(a, 0, p);
+        const uint32_t* L = list_ptr(a, p);
         constexpr int WCH = (2 * MAX_BATCH + 2 + 63) / 64;
         uint32_t xw[WCH];
         bool ow[WCH];
@@ -1695,7 +1695,7 @@ __global__ void __launch_bounds__(SP_THREADS) commit_spec_kernel(CommitArgs a) {
         int cat = -1;
         if (q2 < B) {
           const int so = dso[q2 * SB + jb.slot];
-          const LevelHdr* h = hdr_ptr(a, 0, q2);
+          const LevelHdr* h = hdr_ptr(a, q2);
           const LevelExt* x = reinterpret_cast<const LevelExt*>(a.xbase + (size_t)a.bmax * LCAP * 4 +
                                                                 (size_t)a.bmax * sizeof(LevelHdr)) + q2;
           const int nl = min(x->nlev, LEVALL);

@@ -1306,11 +1306,8 @@ CommitArgs commit_args(gs_ctx* c, const Slot& s, int b) {
   a.seq = s.d_seq;
   a.npods = b;
   a.nranks = lvl_ranks(c);
-  a.shard_size = (c->N + a.nranks - 1) / a.nranks;
-  // several ranks: the speculative commit reads the merged levels, the pipelined / lockstep kernels every rank block
-  a.xbase = a.nranks == 1 ? (cand_overlapped(c, s) ? s.d_lst.get() : c->d_xchg_send.get())
-                            : commit_spec_selected(c->window_k) ? c->d_xmerged.get() : c->d_xchg_recv.get();
-  a.xblock = c->xchg_bytes;
+  // several level shards: the speculative commit reads their merged levels
+  a.xbase = a.nranks == 1 ? (cand_overlapped(c, s) ? s.d_lst.get() : c->d_xchg_send.get()) : c->d_xmerged.get();
   a.bmax = c->B;
   a.pf = c->pf;
   a.seed = c->cfg.seed;
@@ -1533,7 +1530,6 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
   if (lvl_ranks(c) > 1) {
     int rc = exchange(c, XSITE_LEVELS, c->d_xchg_send.get(), c->d_xchg_recv.get(), c->xchg_bytes);
     if (rc) return rc;
-    if (!commit_spec_selected(c->window_k)) return fail(c, GS_EUNSUPPORTED, "several ranks need the speculative commit");
     HIP_TRY(c, launch_merge_levels(c->d_xchg_recv.get(), c->xchg_bytes, c->nranks, b, c->B, c->lstride,
                                    c->d_xmerged.get(), s.d_xerr, st));
   }
@@ -2497,24 +2493,22 @@ void report_commit_stamps(const gs_ctx* c) {
             "%.0f, lists %.0f; the block's slowest landed-row lane: row loads %.0f, loads + evaluation %.0f; thread 0: "
             "start -> its evaluation %.0f, start -> every lane evaluated %.0f\n",
             sa[517] / nb, sa[518] / nb, sa[519] / nb, sa[520] / nb, sa[521] / nb, sa[522] / nb, sa[523] / nb);
-  } else {   // the lockstep commit kernel (node sampling): region 0
-    uint64_t st[32] = {};
-    if (hipMemcpy(st, c->d_stamps.get(), 256, hipMemcpyDeviceToHost) != hipSuccess) return;
+  } else {   // commit_window_kernel (node sampling): thread 0's stamps 7..11, thread 128's 12 and 13
+    // a stamp takes the time since the thread's previous one: a pod's window selection and winner fetch count in
+    // the first stamp after them (the Reserve's pair evaluation where the pod has one, else the assume)
+    uint64_t st[14] = {};
+    if (hipMemcpy(st, c->d_stamps.get(), sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return;
+    const double np = c->stats_all_pods ? (double)c->stats_all_pods : 1.0;
     uint64_t tot = 0;
-    for (int i = 0; i < 12; ++i) tot += st[i];
-    fprintf(stderr, "gpuscore commit phases (s_memtime ticks, %% of %llu):", (unsigned long long)tot);
-    for (int i = 0; i < 12; ++i) fprintf(stderr, " p%d=%.1f%%", i, tot ? 100.0 * st[i] / tot : 0.0);
-    fprintf(stderr, "\n  raw ticks per committed pod (%llu pods):", (unsigned long long)c->stats_all_pods);
-    for (int i = 0; i < 22; ++i)
-      fprintf(stderr, " s%d=%.0f", i, c->stats_all_pods ? (double)st[i] / (double)c->stats_all_pods : 0.0);
-    fprintf(stderr, "\n  pods through full-row resolution %llu, FitError %llu, slow path %llu",
-            (unsigned long long)st[18], (unsigned long long)st[19], (unsigned long long)st[20]);
-    fprintf(stderr, ", winners on NUMA-policy rows %llu, fresh winners %llu, cpuset pods %llu | s24 (Reserve pair "
-            "evaluation) %.0f", (unsigned long long)st[22], (unsigned long long)st[23], (unsigned long long)st[25],
-            c->stats_all_pods ? (double)st[24] / (double)c->stats_all_pods : 0.0);
-    fprintf(stderr, " | s26 (full-row resolution, per such pod) %.0f", st[18] ? (double)st[26] / (double)st[18] : 0.0);
-    fprintf(stderr, " | policy-row rescoring: %llu pods, %.0f ticks per pair (thread 128)\n",
-            (unsigned long long)st[12], st[12] ? (double)st[13] / st[12] : 0.0);
+    for (int i = 7; i < 12; ++i) tot += st[i];
+    auto P = [&](int i) { return tot ? 100.0 * (double)st[i] / (double)tot : 0.0; };
+    fprintf(stderr, "gpuscore window commit, thread 0 (s_memtime ticks, %% of %llu; %llu pods, %.0f ticks per pod): "
+            "selection + Reserve pair evaluation %.1f%% | device cpuset Reserve %.1f%% | selection (pods without the "
+            "pair evaluation) + assume %.1f%% | re-scoring of a NUMA-policy row %.1f%% | of another row %.1f%%\n",
+            (unsigned long long)tot, (unsigned long long)c->stats_all_pods, (double)tot / np, P(10), P(11), P(7), P(8),
+            P(9));
+    fprintf(stderr, "  policy-row re-scoring: %llu pods, %.0f ticks per pair (thread 128)\n", (unsigned long long)st[12],
+            st[12] ? (double)st[13] / (double)st[12] : 0.0);
   }
 }
 }  // namespace

@@ -260,20 +260,16 @@ __host__ __device__ inline void tiebreak_records(uint64_t seed, uint64_t seq, in
 
 
 // ------------------------------------------------------------------------------------------------
-// Sequential commit: ONE wave walks the batch's pods in order (no workgroup barriers: LDS traffic of a
-// single wave is in order, so phases only need compiler scheduling fences, and global prefetches of the
-// next pod's headers stay in flight while the current pod is resolved).
-//
-// For pod k the effective score of a node is its batch-start score (S, summarized per shard by the listed
-// levels) unless an earlier pod of the batch landed on it ("dirty"): dirty rows live in LDS and their
-// scores for every later pod are re-evaluated exactly (dso = batch-start score, dsc = current score).
-// The max M is valid when it exceeds every shard's highest unlisted score (`next`); otherwise the batch
-// is cut at k. Ties at M are ordered by node index across shards (shards are contiguous ranges).
-constexpr int COMMIT_WAVES = 4, COMMIT_THREADS = 64 * COMMIT_WAVES;   // commit workgroup
+// The two commit kernels take a batch's pods in order and share what follows: for pod k a node's score is its
+// batch-start score (the rows S) unless an earlier pod of the batch landed on it ("dirty"); dirty rows live in LDS
+// behind a node hash, get the assume + Reserve deltas there, are re-scored exactly for the later pods and are
+// written back when the batch ends. commit_spec_kernel (gs_commit_spec.hip) selects over the candidate levels and
+// runs whenever every node is scored; commit_window_kernel (gs_kernels.hip) selects over the rotation window and
+// runs under node sampling.
+constexpr int COMMIT_WAVES = 4, COMMIT_THREADS = 64 * COMMIT_WAVES;   // commit_window_kernel's workgroup
 constexpr int HASH = 1024;
 constexpr int POD_STRIDE = 136;   // LDS bytes per pod vector in the commit kernel (sizeof(PodVec) + 8)
 static_assert(POD_STRIDE >= (int)sizeof(PodVec) && POD_STRIDE % 8 == 0, "pod stride");
-constexpr int WIN = 2 * MAX_BATCH + 8;
 #define WAVE_FENCE() __builtin_amdgcn_wave_barrier()
 
 __device__ __forceinline__ int32_t row_score(const Row& d, const PodVec& p, const Profile& pf, const MirrorView& m,
@@ -298,11 +294,12 @@ __device__ __forceinline__ int hash_find(const int32_t* hkey, const int32_t* hva
   return -1;
 }
 
-__device__ __forceinline__ const LevelHdr* hdr_ptr(const CommitArgs& a, int r, int k) {
-  return reinterpret_cast<const LevelHdr*>(a.xbase + (size_t)r * a.xblock + (size_t)a.bmax * LCAP * 4) + k;
+// pod k's level header and node lists in the level block (CommitArgs.xbase)
+__device__ __forceinline__ const LevelHdr* hdr_ptr(const CommitArgs& a, int k) {
+  return reinterpret_cast<const LevelHdr*>(a.xbase + (size_t)a.bmax * LCAP * 4) + k;
 }
-__device__ __forceinline__ const uint32_t* list_ptr(const CommitArgs& a, int r, int k) {
-  return reinterpret_cast<const uint32_t*>(a.xbase + (size_t)r * a.xblock) + (size_t)k * LCAP;
+__device__ __forceinline__ const uint32_t* list_ptr(const CommitArgs& a, int k) {
+  return reinterpret_cast<const uint32_t*>(a.xbase) + (size_t)k * LCAP;
 }
 
 // Wave64 reductions and scan over DPP row operations (no LDS round trip, unlike __shfl_*: ds_bpermute). All 64
@@ -346,19 +343,6 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
   v += GS_DPP(0, v, 0x142, 0xA);
   v += GS_DPP(0, v, 0x143, 0xC);
   return v;
-}
-
-// sort n (<= 128) distinct node ids in place, tmp as scratch (one wave)
-__device__ __forceinline__ void wave_rank_sort(uint32_t* v, int n, uint32_t* tmp, int lane) {
-  for (int i = lane; i < n; i += 64) {
-    uint32_t x = v[i];
-    int r = 0;
-    for (int u = 0; u < n; ++u) r += v[u] < x;
-    tmp[r] = x;
-  }
-  WAVE_FENCE();
-  for (int i = lane; i < n; i += 64) v[i] = tmp[i];
-  WAVE_FENCE();
 }
 
 // The device Reserve selects this pod's cpuset on this row: its topology is in the device scope (topo >= 0), and the

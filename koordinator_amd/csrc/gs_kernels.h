@@ -81,12 +81,11 @@ struct CommitArgs {
   const PodVec* pods;
   const uint64_t* seq;
   int npods;
-  int nranks;
-  uint32_t shard_size;       // ceil(N / nranks): shard of node i = i / shard_size
-  const uint8_t* xbase;      // rank r block at xbase + r*xblock: [npods_max x LCAP u32 lists | LevelHdr x npods_max |
-                             //  LevelExt x npods_max]
-  size_t xblock;
-  int bmax;                  // pods per block layout (lists/hdrs are laid out for bmax pods)
+  int nranks;                // level shards (the speculative commit reads their merged levels; node sampling: 1)
+  const uint8_t* xbase;      // the level block: [npods_max x LCAP u32 lists | LevelHdr x npods_max | LevelExt x npods_max]
+                             // (several shards: the one launch_merge_levels wrote; unused under node sampling)
+  const int32_t* xerr;       // several shards: nonzero = the all-gathered blocks' exchange tags disagree (merge_levels)
+  int bmax;                // pods per block layout (lists/hdrs are laid out for bmax pods)
   Profile pf;
   uint64_t seed;
   int32_t forced_node;       // >= 0: pod 0 was resolved by the exact full-row path
@@ -100,7 +99,8 @@ struct CommitArgs {
   const uint8_t* aff;        // [pod][ld] Filter-time affinity of NUMA-policy nodes of the own shard (eval_numa_kernel)
   uint32_t ld;
   uint32_t own0, own1;       // this rank's shard [own0, own1)
-  const int16_t* S;          // batch-start score rows (one shard only: in-kernel full-row resolution; else nullptr)
+  const int16_t* S;          // batch-start score rows (one shard only: the rotation window, the speculative kernel's
+                             // full-row resolution; else nullptr)
   const int16_t* S_own;      // this rank's batch-start score rows (batch-start scores of fresh own-shard rows)
   const int32_t* prev;       // speculative pass: the previous batch's committed[4]; run only if prev[1] == 1
   // node sampling (gs_config.sample_nodes, one shard): window_k = numFeasibleNodesToFind(N) (0 = every node);
@@ -111,7 +111,6 @@ struct CommitArgs {
   int32_t* tb;               // [npods x TB_N] selectHost tie-break records of each pod (speculative commit)
   int32_t tb_ready;          // cand_kernel wrote tb beside the previous commit (0: the commit's prologue computes it)
   uint8_t* landed;           // the batch's landed slab out (speculative commit; nullptr: none), see LANDED_* below
-  const int32_t* xerr;       // several shards: nonzero = the all-gathered blocks' exchange tags disagree (merge_levels)
 };
 // The landed slab: the rows a batch's committed pods landed on, as the speculative commit kernel leaves them (the
 // state its write-back gives the mirror), distinct nodes, rows with a NUMA topology policy first: int32 count, int32
@@ -215,8 +214,9 @@ hipError_t launch_merge_levels(const uint8_t* xin, size_t xblock, int nranks, in
 hipError_t launch_unpack_scores(const uint8_t* xin, size_t xblock, int nranks, int npods, uint32_t per, uint32_t pld,
                                 uint32_t N, int16_t* S, uint8_t* aff, uint32_t ld, int32_t* xerr, hipStream_t st);
 size_t commit_smem_bytes(int B);
-bool commit_spec_selected(uint32_t window_k);   // the speculative commit kernel runs (else pipelined / lockstep)
-hipError_t launch_commit(const CommitArgs& a, hipStream_t st);        // window_k > 0: lockstep kernel
+bool commit_spec_selected(uint32_t window_k);   // the speculative commit kernel runs (else commit_window_kernel)
+// window_k > 0: commit_window_kernel (one level shard with its score rows, else hipErrorInvalidValue)
+hipError_t launch_commit(const CommitArgs& a, hipStream_t st);
 hipError_t launch_commit_spec(const CommitArgs& a, hipStream_t st);   // speculative pipeline (gs_commit_spec.hip)
 hipError_t set_commit_spec_attributes();
 hipError_t launch_row_stats(const int16_t* S, uint32_t len, RowStat* out, hipStream_t st);

@@ -5,9 +5,9 @@
 //                      filter + Fit LeastAllocated score + LoadAware score + weighted sum -> int16 rows
 //   cand_kernel        per pod: per-wave histograms -> top score levels -> order-preserving compaction of
 //                      every node of those levels (node index order) -> LevelHdr + level lists
-//   commit_kernel      one workgroup: the batch's pods in order — selectHost over (listed levels of every
-//                      shard, minus/plus the rows earlier pods of the batch landed on, re-scored exactly),
-//                      then assume/Reserve deltas; cuts the batch if a pod's levels are exhausted
+//   commit_window_kernel   the commit under node sampling, one workgroup: the batch's pods in order — selectHost
+//                      over the rotation window of the score rows (the rows earlier pods of the batch landed on
+//                      re-scored exactly), then assume/Reserve deltas. Every other batch: gs_commit_spec.hip
 //   row_stats_kernel / row_select_kernel   exact full-row path (a level too large to list)
 //   scatter_rows_kernel   host -> HBM delta rows (AoS staging -> SoA columns)
 //
@@ -1158,11 +1158,13 @@ extern "C" int gsx_tiebreak_selftest(uint64_t seed, int iters, char* msg, size_t
   return bad;
 }
 
-// ST: diagnostic build with s_memtime phase stamps (accumulated per phase, written to a.stamps)
+// The commit under node sampling (window_k > 0), one level shard: one workgroup takes the batch's pods in order. All
+// waves select pod k's node over the rotation window (window_select), wave 0 fetches the winner's row, thread 0 runs
+// assume + Reserve, then all waves re-score the winner row for the later pods.
+// ST: diagnostic build with s_memtime phase stamps (accumulated per phase, written to a.stamps[7..13])
 template <bool ST>
-__global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
+__global__ void __launch_bounds__(COMMIT_THREADS) commit_window_kernel(CommitArgs a) {
   uint64_t st_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t st_stage = 0;                      // header staging cycles (inside p0)   // numa_eval segments of thread 128's policy-row rescoring (ST)
   uint64_t st_last = ST ? __builtin_amdgcn_s_memtime() : 0;
 #define STAMP(i)                                    \
   do {                                              \
@@ -1174,39 +1176,28 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
   } while (0)
   extern __shared__ __align__(16) unsigned char cm[];
   const int B = a.npods;
-  const int R = a.nranks;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
   // pod vectors at a 136-B stride: the re-scoring threads read different pods, and a 128-B stride would put
   // every lane of a wave on the same two LDS banks
   auto pods = [&](int i) -> PodVec& { return *reinterpret_cast<PodVec*>(cm + (size_t)i * POD_STRIDE); };
   Row* drows = reinterpret_cast<Row*>(cm + (size_t)B * POD_STRIDE);          // B dirty slots
   int16_t* dsc = reinterpret_cast<int16_t*>(drows + B);                      // [pod][slot] current score
-  int16_t* dso = dsc + B * B;                                                // [pod][slot] batch-start score
   // offsets from the LDS base, not integer-cast pointers: the address space stays visible to the compiler (an
   // integer round trip turns every access into a flat load that waits on outstanding global loads)
-  const size_t hoff = ((size_t)B * POD_STRIDE + (size_t)B * sizeof(Row) + (size_t)B * B * 4 + 15) & ~(size_t)15;
+  const size_t hoff = ((size_t)B * POD_STRIDE + (size_t)B * sizeof(Row) + (size_t)B * B * 2 + 15) & ~(size_t)15;
   int32_t* hkey = reinterpret_cast<int32_t*>(cm + hoff);                     // HASH
   int32_t* hval = hkey + HASH;                                               // HASH
   CpuStateDev* cst = reinterpret_cast<CpuStateDev*>(hval + HASH);            // B dirty slots: CPU state
 
-  __shared__ int32_t sh_score[MAX_RANKS * MAXLEV], sh_count[MAX_RANKS * MAXLEV], sh_dec[MAX_RANKS * MAXLEV];
-  __shared__ uint32_t dnew[MAX_BATCH], tmp[MAX_BATCH];
-  __shared__ uint32_t win[WIN];
-  __shared__ int32_t pre_old[WIN + 1];
   __shared__ Row orow;                                  // batch-start copy of a freshly dirtied row
-  __shared__ int s_action, s_slot, s_fresh, s_M, s_F;  // wave-0 decision for pod k (0 commit, 1 skip, 2 cut,
-                                                       // 3 resolve from the full row)
-  // a pod resolved from its whole score row (host slow path for pod 0, or in-kernel on one shard): its selectHost
-  __shared__ int s_fk, s_fnode, s_fscore, s_ffeas, s_Md, s_Fd, s_ndc;
-  __shared__ int64_t s_fties;
-  __shared__ int s_red[2 * COMMIT_WAVES];
+  __shared__ int s_action, s_slot, s_fresh, s_M, s_F;  // the decision for pod k (0 commit, 1 skip, 2 cut)
+  __shared__ int s_tie;                                // the node of the selected tie in the window (-1: not located)
   __shared__ uint32_t s_winner;
   __shared__ int64_t s_T;
   __shared__ int s_cut;                                // the pod just committed needs host-side Reserve
   __shared__ int s_aff;                                // known affinity of pod k on its winner row (-1: recompute)
   __shared__ uint64_t s_cpuset[4];                     // CPUs of a device-side cpuset Reserve
-  __shared__ HintTable s_ht, s_ht2;                    // NUMA hint sums of the winner row (new / batch-start state)
+  __shared__ HintTable s_ht;                           // NUMA hint sums of the winner row
   const bool numa_on = (a.pf.enabled & 0x30u) != 0;
   const uint64_t rt0 = __builtin_amdgcn_s_memrealtime();   // the kernel's duration -> committed[4] (100 MHz ticks)
   // speculative pass queued behind another batch: only if that one committed every pod with nothing left for
@@ -1227,12 +1218,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
   __shared__ int32_t s_wend, s_wproc, s_ndirty;       // s_ndirty: dirty slots (wave 0's nd, published)
   if (tid == 0) {
     s_ndirty = 0;
-    s_start = a.window_k ? (a.prev ? (uint32_t)a.prev[2] : a.start) : 0u;
-    s_fk = a.forced_node >= 0 ? 0 : -1;
-    s_fnode = a.forced_node;
-    s_fscore = a.forced_score;
-    s_ffeas = a.forced_feasible;
-    s_fties = a.forced_ties;
+    s_start = a.prev ? (uint32_t)a.prev[2] : a.start;
   }
   // fresh-row fetch map of this wave-0 lane (loop invariant): kind 0 none, 1 i64 column, 2 i32 column, 3 the
   // Filter-time affinity byte, 4 the node index; destination region 0 orow, 1 the slot's CPU state, 2 s_aff
@@ -1257,12 +1243,6 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
   for (int i = tid; i < B; i += COMMIT_THREADS) pods(i) = a.pods[i];
   for (int i = tid; i < HASH; i += COMMIT_THREADS) { hkey[i] = -1; hval[i] = -1; }
   const MirrorView& m = a.m;
-  const int nhl = R * MAXLEV;                    // header lanes: lane = r*MAXLEV + j
-  // LevelHdrs and seq of HCH pods at a time are staged in LDS (one HBM round trip per chunk)
-  constexpr int HCH = 16;
-  __shared__ int32_t hs_score[HCH][MAX_RANKS * MAXLEV], hs_count[HCH][MAX_RANKS * MAXLEV];
-  __shared__ int32_t hs_nlev[HCH][MAX_RANKS], hs_feas[HCH][MAX_RANKS], hs_next[HCH][MAX_RANKS];
-  __shared__ uint64_t hs_seq[HCH];
   int nd = 0;
   int committed = B;
   bool host_cut = false;   // the batch ended at a pod whose cpuset Reserve the host performs
@@ -1403,7 +1383,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
     // the jp-th tie at M in window order (registers hold the single pass when the window ended inside it)
     const int64_t jp = tiebreak_position(a.seed, a.seq[k], T);
     int64_t before = 0;
-    if (tid == 0) s_fnode = -1;
+    if (tid == 0) s_tie = -1;
     for (uint32_t base = 0; base <= wend; base += COMMIT_THREADS * WCH) {
       if (passes > 1) load_pass(base, v);
       int c = 0;
@@ -1419,7 +1399,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
 #pragma unroll
         for (int j = 0; j < WCH; ++j) {
           const uint32_t i = base + (uint32_t)tid * WCH + j;
-          if (i <= wend && v[j] == M && --need == 0) s_fnode = (int)node_at(i);
+          if (i <= wend && v[j] == M && --need == 0) s_tie = (int)node_at(i);
         }
       }
       before += total;
@@ -1427,280 +1407,18 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
     }
     __syncthreads();
     if (tid == 0) {
-      s_action = s_fnode >= 0 ? 0 : 2;   // 2: unreachable (the tie exists), the host fails loudly
-      s_winner = (uint32_t)s_fnode;
+      s_action = s_tie >= 0 ? 0 : 2;   // 2: unreachable (the tie exists), the host fails loudly
+      s_winner = (uint32_t)s_tie;
       s_M = M; s_F = F; s_T = T;
       s_start = (st0 + proc) % N;
     }
     __syncthreads();
   };
   for (int k = 0; k < B; ++k) {
-   const uint64_t t_stage0 = ST ? __builtin_amdgcn_s_memtime() : 0;
-   if (k % HCH == 0 && !a.window_k) {
-     for (int e = tid; e < HCH * nhl; e += COMMIT_THREADS) {
-       int kk = e / nhl, l = e % nhl;
-       if (k + kk < B) {
-         const LevelHdr* h = hdr_ptr(a, l / MAXLEV, k + kk);
-         hs_score[kk][l] = h->score[l % MAXLEV];
-         hs_count[kk][l] = h->count[l % MAXLEV];
-       }
-     }
-     for (int e = tid; e < HCH * R; e += COMMIT_THREADS) {
-       int kk = e / R, r = e % R;
-       if (k + kk < B) {
-         const LevelHdr* h = hdr_ptr(a, r, k + kk);
-         hs_nlev[kk][r] = h->nlev;
-         hs_feas[kk][r] = h->feasible;
-         hs_next[kk][r] = h->next;
-       }
-     }
-     for (int e = tid; e < HCH; e += COMMIT_THREADS)
-       if (k + e < B) hs_seq[e] = a.seq[k + e];
-     __syncthreads();
-   }
-   if (ST) st_stage += __builtin_amdgcn_s_memtime() - t_stage0;   // header staging share of p0
-   for (;;) {   // one pass; a second, forced one after an in-kernel full-row resolution
-   if (a.window_k) {   // node sampling: findNodesThatPassFilters over the rotation window, then selectHost
-     window_select(k);
-     if (wave == 0 && s_action == 0) fetch_winner(k, s_winner, s_M, s_F, s_T);
-     __syncthreads();
-     break;
-   }
-   if (wave == 0) do {   // ===================== wave 0: selectHost for pod k =====================
-    const int kc = k % HCH;
-    const int r_l = lane / MAXLEV, j_l = lane % MAXLEV;
-    int hs = lane < nhl ? hs_score[kc][lane] : -1, hc = lane < nhl ? hs_count[kc][lane] : 0;
-    const int feas_l = lane < R ? hs_feas[kc][lane] : 0, next_l = lane < R ? hs_next[kc][lane] : -1;
-    const uint64_t seqk = hs_seq[kc];
-    const bool lvl = lane < nhl && j_l < hs_nlev[kc][r_l < MAX_RANKS ? r_l : 0];
-    if (!lvl) { hs = -1; hc = 0; }
-    if (lane < nhl) { sh_score[lane] = hs; sh_count[lane] = hc; sh_dec[lane] = 0; }
-    WAVE_FENCE();
-    STAMP(0);
-    const bool forced = k == s_fk;
-    // ---- dirty rows: batch-start / current scores of pod k, listed-level decrements
-    int Md = -1, Fd = 0;
-    for (int s = lane; s < nd; s += 64) {
-      int sc = dsc[k * B + s], so = dso[k * B + s];
-      Md = max(Md, sc);
-      Fd += (sc >= 0 ? 1 : 0) - (so >= 0 ? 1 : 0);
-      if (so >= 0) {
-        int base = (int)(drows[s].node / a.shard_size) * MAXLEV;
-        for (int j = 0; j < MAXLEV; ++j)
-          if (sh_score[base + j] == so) { atomicAdd(&sh_dec[base + j], 1); break; }
-      }
-    }
-    Md = wave_max(Md);
-    Fd = wave_sum(Fd);
-    WAVE_FENCE();
-    STAMP(1);
-    const int clean = lvl ? hc - sh_dec[lane] : 0;
-    int M = max(wave_max(clean > 0 ? hs : -1), Md);
-    int F = Fd + wave_sum(lane < R ? feas_l : 0);
-    if (forced) {
-      M = s_fscore;
-      F = s_ffeas;
-    } else if (__ballot(lane < R && M <= next_l)) {
-      // a shard may hold unlisted nodes at M: one shard resolves pod k from its whole row right here; with
-      // several shards the batch is cut and the host resolves it (row_stats / row_select / exchange)
-      if (lane == 0) {
-        s_action = (R == 1 && a.S) ? 3 : 2;
-        s_Md = Md;
-        s_Fd = Fd;
-        s_ndc = nd;   // the dirty-slot count lives in wave 0's registers only
-      }
-      break;
-    }
-    if (M < 0) {       // FitError: no feasible node anywhere, nothing assumed
-      if (lane == 0) {
-        a.out[k] = PlacementDev{-1, (uint32_t)F, 0, 0, 0, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-        s_action = 1;
-      }
-      break;
-    }
-    uint32_t winner = 0xffffffffu;
-    int64_t T = 0;
-    STAMP(2);
-    if (forced) {
-      if (s_fnode < 0) { if (lane == 0) s_action = 2; break; }   // unreachable for a valid max: cut, host re-run
-      winner = (uint32_t)s_fnode;
-      T = s_fties;
-    } else {
-      // ---- tie set at M: clean listed nodes + dirty rows now at M ("dnew") - dirty rows listed at M ("old")
-      const int cm_lane = (lvl && hs == M) ? clean : 0;
-      int ndn = 0;
-      for (int s0 = 0; s0 < nd; s0 += 64) {
-        int s = s0 + lane;
-        bool isn = s < nd && dsc[k * B + s] == M;
-        uint64_t bn = __ballot(isn);
-        if (isn) dnew[ndn + __popcll(bn & lt_mask)] = drows[s].node;
-        ndn += __popcll(bn);
-      }
-      WAVE_FENCE();
-      T = (int64_t)wave_sum(cm_lane) + ndn;
-      int64_t jp = tiebreak_position(a.seed, seqk, T);
-      if (ndn > 1) wave_rank_sort(dnew, ndn, tmp, lane);
-      STAMP(3);
-      // per shard: clean ties + dirty ties (lane r < R), owning shard r* by prefix
-      int here = 0;
-      {
-        int c = 0;
-        for (int j = 0; j < MAXLEV; ++j) c += __shfl(cm_lane, (lane < R ? lane : 0) * MAXLEV + j);
-        if (lane < R) {
-          uint32_t sb = (uint32_t)lane * a.shard_size, se = sb + a.shard_size;
-          int dn = 0;
-          for (int u = 0; u < ndn; ++u) dn += dnew[u] >= sb && dnew[u] < se;
-          here = c + dn;
-        }
-      }
-      int incl = here;
-      for (int off = 1; off < 64; off <<= 1) {
-        int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      uint64_t hit = __ballot(lane < R && incl >= jp);
-      const int rstar = hit ? (__ffsll((long long)hit) - 1) : (R - 1);
-      jp -= __shfl(incl - here, rstar);
-      // level-M segment of r*'s list
-      int off = 0, len = 0;
-      for (int j = 0; j < MAXLEV; ++j) {
-        int sc = sh_score[rstar * MAXLEV + j];
-        if (sc < 0) break;
-        if (sc == M) { len = sh_count[rstar * MAXLEV + j]; break; }
-        off += sh_count[rstar * MAXLEV + j];
-      }
-      const uint32_t sb = (uint32_t)rstar * a.shard_size, se = sb + a.shard_size;
-      int nn_lo = 0;
-      while (nn_lo < ndn && dnew[nn_lo] < sb) ++nn_lo;
-      int nn_hi = nn_lo;
-      while (nn_hi < ndn && dnew[nn_hi] < se) ++nn_hi;
-      // dirty rows of r* listed at M (batch-start score M)
-      int ndo_r = 0;
-      for (int s = lane; s < nd; s += 64) {
-        uint32_t node = drows[s].node;
-        ndo_r += (dso[k * B + s] == M && node >= sb && node < se) ? 1 : 0;
-      }
-      ndo_r = wave_sum(ndo_r);
-      const int lo = (int)max<int64_t>(0, jp - 2 - (nn_hi - nn_lo));
-      const int hi = (int)min<int64_t>(len - 1, jp - 1 + ndo_r);
-      const int W = hi - lo + 1;
-      // ---- the jp-th node of (listed level-M nodes of r* - old) U dnew, node order, over window L[lo..hi]
-      const uint32_t* L = list_ptr(a, rstar, k) + off;
-      uint32_t cand = 0xffffffffu;
-      if (len > 0) {
-        for (int i = lane; i < W; i += 64) win[i] = L[lo + i];
-        WAVE_FENCE();
-        STAMP(4);
-        // old rows before the window, then a running count over the window (membership via the hash)
-        int base_old = 0;
-        for (int s = lane; s < nd; s += 64) {
-          uint32_t node = drows[s].node;
-          base_old += (dso[k * B + s] == M && node >= sb && node < win[0]) ? 1 : 0;
-        }
-        base_old = wave_sum(base_old);
-        int running = base_old;
-        for (int i0 = 0; i0 < W; i0 += 64) {
-          int i = i0 + lane;
-          uint32_t x = i < W ? win[i] : 0xffffffffu;
-          bool isold = false;
-          if (i < W) {
-            int sl = hash_find(hkey, hval, x);
-            isold = sl >= 0 && dso[k * B + sl] == M;
-          }
-          uint64_t bo = __ballot(isold);
-          int older = running + __popcll(bo & lt_mask);
-          if (i < W) {
-            pre_old[i] = older;
-            int newer = 0;
-            for (int u = nn_lo; u < nn_hi; ++u) newer += dnew[u] < x;
-            if (!isold && (int64_t)(lo + i - older + newer + 1) == jp) cand = x;
-          }
-          running += __popcll(bo);
-        }
-        if (lane == 0) pre_old[W] = running;
-        WAVE_FENCE();
-      }
-      for (int u0 = nn_lo + lane; u0 < nn_hi; u0 += 64) {
-        uint32_t n = dnew[u0];
-        int64_t ltn = -1;   // #listed level-M nodes < n, when it can decide position jp
-        int older = 0;
-        if (len == 0) {
-          ltn = 0;
-        } else {
-          int p = 0, q = W;      // lower_bound(win, n)
-          while (p < q) { int mid = (p + q) >> 1; if (win[mid] < n) p = mid + 1; else q = mid; }
-          if (p == 0) ltn = (lo == 0) ? 0 : -1;
-          else if (p == W) ltn = (hi == len - 1) ? len : -1;
-          else ltn = lo + p;
-          older = pre_old[p];
-        }
-        if (ltn >= 0 && ltn - older + (u0 - nn_lo) + 1 == jp) cand = n;
-      }
-      uint64_t got = __ballot(cand != 0xffffffffu);
-      if (!got) { if (lane == 0) s_action = 2; break; }   // unreachable for a valid max: cut, exact re-run
-      winner = __shfl(cand, __ffsll((long long)got) - 1);
-    }
-    STAMP(5);
-    fetch_winner(k, winner, M, F, T);
-    STAMP(6);
-   } while (0);
+    // findNodesThatPassFilters over the rotation window, then selectHost
+    window_select(k);
+    if (wave == 0 && s_action == 0) fetch_winner(k, s_winner, s_M, s_F, s_T);
     __syncthreads();
-    if (s_action != 3) break;
-    // ---- exact full-row resolution of pod k on the single shard: batch-start scores S[k][*] for clean nodes,
-    // current scores for dirty rows; max, ties and feasible count, then the j*-th tie in node order
-    {
-      const int16_t* row = a.S + (size_t)k * a.ld;
-      const uint32_t len = a.own1 - a.own0, chunk = (len + COMMIT_THREADS - 1) / COMMIT_THREADS;
-      const uint32_t i0 = min(len, (uint32_t)tid * chunk), i1 = min(len, i0 + chunk);
-      int lmax = -1, lfeas = 0;
-      for (uint32_t i = i0; i < i1; ++i) {
-        const int x = row[i];
-        lfeas += x >= 0 ? 1 : 0;
-        if (x > lmax && hash_find(hkey, hval, a.own0 + i) < 0) lmax = x;
-      }
-      lmax = wave_max(lmax);
-      lfeas = wave_sum(lfeas);
-      if (lane == 0) { s_red[wave] = lmax; s_red[COMMIT_WAVES + wave] = lfeas; }
-      __syncthreads();
-      int M = s_Md, F = s_Fd;
-      for (int w = 0; w < COMMIT_WAVES; ++w) { M = max(M, s_red[w]); F += s_red[COMMIT_WAVES + w]; }
-      __syncthreads();
-      int cnt = 0;
-      if (M >= 0) {
-        for (uint32_t i = i0; i < i1; ++i)
-          if (row[i] == M && hash_find(hkey, hval, a.own0 + i) < 0) ++cnt;
-        for (int s = 0; s < s_ndc; ++s) {
-          const uint32_t n = drows[s].node;
-          if (n >= a.own0 + i0 && n < a.own0 + i1 && dsc[k * B + s] == M) ++cnt;
-        }
-      }
-      int incl = cnt;
-      for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-      }
-      if (lane == 63) s_red[wave] = incl;
-      __syncthreads();
-      int base = 0;
-      for (int w = 0; w < wave; ++w) base += s_red[w];
-      int64_t T = 0;
-      for (int w = 0; w < COMMIT_WAVES; ++w) T += s_red[w];
-      const int64_t jp = T > 0 ? tiebreak_position(a.seed, hs_seq[k % HCH], T) : 0;
-      const int64_t excl = base + incl - cnt;
-      if (tid == 0) s_fnode = -1;
-      __syncthreads();
-      if (T > 0 && jp > excl && jp <= excl + cnt) {   // this thread's chunk holds the jp-th tie
-        int64_t need = jp - excl;
-        for (uint32_t i = i0; i < i1; ++i) {
-          const int sl = hash_find(hkey, hval, a.own0 + i);
-          const bool tie = sl >= 0 ? dsc[k * B + sl] == M : row[i] == M;
-          if (tie && --need == 0) { s_fnode = (int)(a.own0 + i); break; }
-        }
-      }
-      if (tid == 0) { s_fk = k; s_fscore = M; s_fties = T; s_ffeas = F; }
-      __syncthreads();
-    }
-   }
     // ===================== all waves: assume + Reserve, re-score later pods =====================
     const int action = s_action;
     if (action == 2) { committed = k; break; }
@@ -1718,8 +1436,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
       const Row dr = fresh ? orow : d;   // registers: the Reserve's pair evaluation re-reads row words
       if (fresh) d = dr;
       const PodVec& pk = pods(k);
-      const bool forced = k == s_fk;
-      PlacementDev pl{(int32_t)s_winner, (uint32_t)s_F, (int64_t)s_M, (uint32_t)s_T, forced ? 1u : 0u, 0, 0,
+      PlacementDev pl{(int32_t)s_winner, (uint32_t)s_F, (int64_t)s_M, (uint32_t)s_T, 0u, 0, 0,
                       {0, 0, 0, 0}, {0, 0, 0, 0}};
       s_cut = 0;
       const uint32_t nf = dr.nr.nflags;
@@ -1783,8 +1500,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
       }
     }
     // NUMA-policy winner row: wave 0 builds the hint table of its new state (one entry per lane) for the
-    // re-scoring lanes; wave 1 that of a fresh row's batch-start state when its batch-start scores are evaluated
-    // (a node outside this rank's shard)
+    // re-scoring lanes
     if (wv == 0 && numa_on) {
       WAVE_FENCE();
       const uint32_t nfw = d.nr.nflags;
@@ -1792,37 +1508,23 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
         const NumaRow nr = d.nr;
         hint_table_fill(s_ht, nr, zone_avail(nr), lane);
       }
-    } else if (wv == 1 && numa_on && fresh && !(orow.node >= a.own0 && orow.node < a.own1)) {
-      const NumaRow nr = orow.nr;
-      if ((nr.nflags >> NF_POLICY_SHIFT) & 3u) hint_table_fill(s_ht2, nr, zone_avail(nr), lane);
     }
     __syncthreads();
     if (s_cut) { committed = k + 1; host_cut = true; break; }
     if (tid == 0) STAMP(7);
     // Re-scoring, pods q = k+1 .. over the waves, RS_PODS per wave: lanes 0..RS_PODS-1 evaluate the winner row's
-    // current score (one row for all lanes: the NUMA hint sums come from the table); lanes 32.. of a fresh row fetch
-    // its batch-start score from the score rows S when the node is in this rank's shard, else evaluate it.
+    // current score (one row for all lanes: the NUMA hint sums come from the table); lanes 32.. are idle.
     {
       constexpr int RS_PODS = MAX_BATCH / COMMIT_WAVES;
       const int sub = lane & 31;
       const bool cur = lane < 32;
       const int q = sub < RS_PODS ? k + 1 + wv * RS_PODS + sub : B;
       const uint64_t t0_ = ST ? __builtin_amdgcn_s_memtime() : 0;
-      const uint32_t node = d.node;
-      const bool own = node >= a.own0 && node < a.own1;
-      const bool load_so = !cur && fresh && own && q < B;
-      int16_t so = 0;
-      if (load_so) so = a.S_own[(size_t)q * a.ld + (node - a.own0)];
       const bool policy_row = numa_on && ((d.nr.nflags >> NF_POLICY_SHIFT) & 3u);   // (ST stamps)
       if (q < B && cur) {   // the row is wave-uniform (LDS at a uniform slot): its words can live in SGPRs
         const Row rr = d;
         dsc[q * B + slot] = (int16_t)row_score(rr, pods(q), a.pf, m, &s_ht);
       }
-      if (fresh && !own && q < B && !cur) {   // several ranks only
-        const Row rr = orow;
-        dso[q * B + slot] = (int16_t)row_score(rr, pods(q), a.pf, m, &s_ht2);
-      }
-      if (load_so) dso[q * B + slot] = so;
       if (ST && tid == 128 && policy_row) {
         st_acc[12] += 1;
         st_acc[13] += __builtin_amdgcn_s_memtime() - t0_;
@@ -1868,8 +1570,7 @@ __global__ void __launch_bounds__(COMMIT_THREADS) commit_kernel(CommitArgs a) {
     a.committed[4] = (int32_t)(__builtin_amdgcn_s_memrealtime() - rt0);
   }
   if (ST && tid == 0) {
-    for (int i = 0; i < 12; ++i) a.stamps[i] += st_acc[i];
-    a.stamps[24] += st_stage;
+    for (int i = 7; i < 12; ++i) a.stamps[i] += st_acc[i];
   }
   if (ST && tid == 128) {
     a.stamps[12] += st_acc[12];
@@ -2107,7 +1808,7 @@ hipError_t launch_cand(int16_t* S, uint32_t ld, uint32_t len, uint32_t n0, int n
 }
 
 size_t commit_smem_bytes(int B) {
-  size_t b = (size_t)B * POD_STRIDE + (size_t)B * sizeof(Row) + (size_t)B * B * 2 * 2;
+  size_t b = (size_t)B * POD_STRIDE + (size_t)B * sizeof(Row) + (size_t)B * B * 2;
   b = (b + 15) & ~(size_t)15;
   b += (size_t)HASH * 8 + 16;
   b += (size_t)B * sizeof(CpuStateDev);
@@ -2115,16 +1816,18 @@ size_t commit_smem_bytes(int B) {
 }
 
 // The speculative commit kernel runs every batch except under node sampling, whose rotation window is resolved by
-// commit_kernel (one shard).
+// commit_window_kernel (one level shard).
 bool commit_spec_selected(uint32_t window_k) { return !window_k; }
 
 hipError_t launch_commit(const CommitArgs& a, hipStream_t st) {
   // several shards: the speculative kernel reads the merged levels (launch_merge_levels)
   if (commit_spec_selected(a.window_k)) return launch_commit_spec(a, st);
+  // the window is resolved over whole score rows: one level shard (several ranks exchange their score rows)
+  if (a.nranks != 1 || a.S == nullptr) return hipErrorInvalidValue;
   if (a.stamps)
-    hipLaunchKernelGGL(commit_kernel<true>, dim3(1), dim3(COMMIT_THREADS), commit_smem_bytes(a.npods), st, a);
+    hipLaunchKernelGGL(commit_window_kernel<true>, dim3(1), dim3(COMMIT_THREADS), commit_smem_bytes(a.npods), st, a);
   else
-    hipLaunchKernelGGL(commit_kernel<false>, dim3(1), dim3(COMMIT_THREADS), commit_smem_bytes(a.npods), st, a);
+    hipLaunchKernelGGL(commit_window_kernel<false>, dim3(1), dim3(COMMIT_THREADS), commit_smem_bytes(a.npods), st, a);
   return hipGetLastError();
 }
 
@@ -2151,10 +1854,10 @@ hipError_t launch_scatter_rows(const MirrorView& m, const uint32_t* idx, const i
 hipError_t set_kernel_attributes() {
   hipError_t e = set_commit_spec_attributes();
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(commit_kernel<false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit_smem_bytes(MAX_BATCH));
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(commit_window_kernel<false>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit_smem_bytes(MAX_BATCH));
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(commit_kernel<true>),
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(commit_window_kernel<true>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)commit_smem_bytes(MAX_BATCH));
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(cand_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -88,18 +88,28 @@ def test_sampling_refuses_several_ranks_under_levels(monkeypatch):
         e.comm_init_callback(2, 0, lambda send: [send, send])
 
 
-@pytest.mark.parametrize("n,pct", [(2, 0), (3, 10)])
-def test_sampling_on_several_ranks_score_rows(n, pct):
+@pytest.mark.parametrize("n,pct,numa", [pytest.param(2, 0, False, id="2-0"), pytest.param(3, 10, False, id="3-10"),
+                                        pytest.param(2, 0, True, id="2-0-numa")])
+def test_sampling_on_several_ranks_score_rows(n, pct, numa):
     """Node sampling on several ranks (threads over the in-process device transport, score-row exchange): every rank
     holds every node's scores after the all-gather and resolves the rotation window itself; placements and
-    nextStartNodeIndex of every rank equal the oracle's."""
+    nextStartNodeIndex of every rank equal the oracle's. numa: test_sampling_numa_profile's cluster (NUMA-policy nodes,
+    cpuset pods) under every plugin: the winner's Filter-time affinity comes from the all-gathered rows, and the
+    Reserve's flags equal the oracle's too."""
     import threading
     from koordinator_amd.engine import Engine, LocalGroup
-    c = loaded_cluster(4000, 500, 18 + n)
-    cfg = config.make_config(c.num_nodes, percentage_of_nodes_to_score=pct)
+    if numa:
+        c = synth.make_cluster(2000, 300, 13)
+        synth.make_numa(c, numa_policy_pct=60, cpuset_pod_pct=30)
+        cfg = config.make_config(c.num_nodes, percentage_of_nodes_to_score=pct, enabled=abi.GS_ENABLE_ALL)
+    else:
+        c = loaded_cluster(4000, 500, 18 + n)
+        cfg = config.make_config(c.num_nodes, percentage_of_nodes_to_score=pct)
     g = LocalGroup(n)
     engines = [Engine(cfg) for _ in range(n)]
     for r, x in enumerate(engines):
+        if numa:
+            x.verify_cpusets(True)
         synth.load_into(x, c)
         x.comm_init_local(g, r)
     seq = np.arange(len(c.pods), dtype=np.uint64)
@@ -107,7 +117,8 @@ def test_sampling_on_several_ranks_score_rows(n, pct):
 
     def run(r):
         try:
-            res[r] = np.concatenate([engines[r].schedule(c.pods[k:k + 250], seq[k:k + 250]) for k in (0, 250)])
+            res[r] = np.concatenate([engines[r].schedule(c.pods[k:k + 250], seq[k:k + 250])
+                                     for k in range(0, len(c.pods), 250)])
         except Exception as ex:   # noqa: BLE001 (reported per rank)
             res[r] = ex
     th = [threading.Thread(target=run, args=(r,)) for r in range(n)]
@@ -120,14 +131,16 @@ def test_sampling_on_several_ranks_score_rows(n, pct):
     want = o.schedule(c.pods, seq)
     for r in range(n):
         assert not isinstance(res[r], Exception) and res[r] is not None, (r, res[r])
-        for f in ("node", "score", "ties", "feasible"):
+        for f in ("node", "score", "ties", "feasible") + (("flags",) if numa else ()):
             assert np.array_equal(res[r][f], want[f]), (r, f)
         assert engines[r].stats()["next_start_node_index"] == o.next_start_node_index
-    assert want["feasible"].max() == orc.num_feasible_nodes_to_find(4000, pct)
+    assert want["feasible"].max() == orc.num_feasible_nodes_to_find(c.num_nodes, pct)
+    if numa:
+        assert (want["flags"] & abi.GS_PLACED_CPUSET).any()
 
 
 def test_sampling_on_several_ranks_diverged_exchange_fails(monkeypatch):
-    """Node sampling on several ranks runs the lockstep commit kernel: it too reads the verdict on the all-gathered
+    """Node sampling on several ranks runs the window commit kernel: it too reads the verdict on the all-gathered
     blocks' exchange tags. A rank whose exchange sequence diverges (GS_DEBUG_XCHG_SKEW=1:1: rank 1 skips a sequence
     number at batch 1) fails every rank with GS_ECOMM naming the batch; nothing is committed on mismatched rows."""
     from tests.test_gpu_parity import run_ranks_local

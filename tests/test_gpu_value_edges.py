@@ -95,7 +95,7 @@ def test_schedule_matches_sequential_oracle(how):
 
 
 def test_schedule_with_node_sampling():
-    """percentageOfNodesToScore = 50: the lockstep commit kernel's own re-score of the edge rows, and the rotation's
+    """percentageOfNodesToScore = 50: the window commit kernel's own re-score of the edge rows, and the rotation's
     start index"""
     c = ve.edge_cluster()
     cfg, want, next_start = ve.oracle_schedule("weighted", 50)
