@@ -1224,6 +1224,22 @@ void set_shard(gs_ctx* c) {
   c->stats.shard_end = c->e1;
 }
 
+// set_shard of a context that may have scheduled already (comm init, after quiesce). The score rows get their -1 padding
+// once, in gs_create; the eval pass rewrites [0, round_up(len, 256)) of a row and the level kernels read
+// [0, round_up(len, 512)), so a row that becomes shorter would keep scores of the longer rows' batches between the two
+// (counted as feasible nodes, listed with node ids of another shard or past N): every slot's rows are filled again.
+int reshard(gs_ctx* c) {
+  const uint32_t n0 = c->n0, n1 = c->n1;
+  set_shard(c);
+  if (c->n0 == n0 && c->n1 == n1) return GS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  HIP_TRY(c, hipStreamSynchronize(c->st_ev.get()));
+  for (Slot& sl : c->slot)
+    if (sl.d_S) HIP_TRY(c, hipMemsetAsync(sl.d_S.get(), 0xff, (size_t)c->B * c->ld * 2, c->st.get()));
+  HIP_TRY(c, hipStreamSynchronize(c->st.get()));
+  return GS_OK;
+}
+
 // ranks whose candidate levels the commit merges: 1 unless the ranks exchange level lists (GS_XCHG=levels)
 int lvl_ranks(const gs_ctx* c) { return c->sgather ? 1 : c->nranks; }
 
@@ -3390,7 +3406,7 @@ int gs_comm_init_rccl(gs_ctx* c, const uint8_t id[128], int nranks, int rank) {
   }
   c->nranks = nranks;
   c->rank = rank;
-  set_shard(c);
+  if (int rc = reshard(c)) return rc;
   c->numa_idx_stale = c->xnuma_stale = true;
   return alloc_exchange(c);
 }
@@ -3405,7 +3421,7 @@ int gs_comm_init_callback(gs_ctx* c, int nranks, int rank, gs_allgather_fn fn, v
   c->cb_user = user;
   c->nranks = nranks;
   c->rank = rank;
-  set_shard(c);
+  if (int rc = reshard(c)) return rc;
   c->numa_idx_stale = c->xnuma_stale = true;
   return alloc_exchange(c);
 }
@@ -3438,7 +3454,7 @@ int gs_comm_init_local(gs_ctx* c, gs_local_group* g, int rank) {
   c->lg = g;
   c->nranks = g->n;
   c->rank = rank;
-  set_shard(c);
+  if (int rc = reshard(c)) return rc;
   c->numa_idx_stale = c->xnuma_stale = true;
   return alloc_exchange(c);
 }
