@@ -486,6 +486,43 @@ int gs_schedule_submit_diag(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, con
  * string, 0), GS_EINVAL for a NULL diagnosis. */
 int gs_fit_error_string(const gs_fit_diagnosis* diag, const char* const* scalar_names, char* buf, size_t len);
 
+/* ---- The per-node status map of a FitError pod ----
+ * Diagnosis.NodeToStatusMap itself: what every PostFilter plugin receives as filteredNodeStatusMap ([upstream]
+ * DefaultPreemption's nodesWherePreemptionMightHelp; ElasticQuota's and Reservation's PostFilter).
+ * Status word of one node in a FitError pod's NodeToStatusMap: the GS_FAIL_* bits of the FIRST failing plugin only
+ * (RunFilterPlugins stops there; order NodeResourcesFit, LoadAwareScheduling, NodeNUMAResource) in bits 0..11,
+ * and in bits 12..15 the resource slots 3..6 that were short (set iff GS_FAIL_FIT_SCALAR is set). */
+#define GS_STATUS_CODE(w)        ((uint32_t)(w) & 0x0FFFu)          /* what gs_reason_string takes */
+#define GS_STATUS_SCALAR_MASK(w) ((((uint32_t)(w) >> 12) & 0xFu) << 3) /* its scalar_mask: exactly the failing slots */
+
+typedef struct gs_status_map {
+  uint16_t* words;        /* in: [cap_rows][num_nodes], caller-owned, valid like out[] */
+  uint32_t  cap_rows;     /* in */
+  int32_t*  row_of;       /* in: [npods]; out: pod i's row in words, or -1 (placed, or no row left) */
+  uint32_t  rows_used;    /* out */
+  uint32_t  rows_dropped; /* out: FitError pods that got no row (cap_rows exhausted); their diag[] is still complete */
+} gs_status_map;
+
+/* gs_schedule_diag / gs_schedule_submit_diag with the map: out[] and diag[] are bit for bit what those calls write,
+ * whatever cap_rows is (0 is allowed: no row). Rows are handed out in queue order: the first cap_rows pods of the
+ * call with out[i].node == -1 get rows 0, 1, ...; row_of[i] >= 0 implies out[i].node == -1. Row r holds at
+ * words[r * num_nodes + n] the status word of node n at that pod's turn; every entry of a handed-out row is
+ * non-zero (a FitError: every node failed), and nothing outside the rows_used handed-out rows is written.
+ * gs_reason_string(GS_STATUS_CODE(w), GS_STATUS_SCALAR_MASK(w), ...) renders a node's status, naming exactly the
+ * scalar slots that were short. Scope and refusals as gs_schedule_diag (GS_EUNSUPPORTED before anything is
+ * scheduled); a NULL map, row_of, or words with cap_rows > 0: GS_EINVAL. The map struct, words and row_of must stay
+ * valid like out (a submission: until gs_schedule_wait returns). A context that never makes these calls allocates
+ * and launches nothing for them. */
+int gs_schedule_diag_nodes(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                           gs_fit_diagnosis* diag, gs_status_map* map);
+int gs_schedule_submit_diag_nodes(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq,
+                                  gs_placement* out, gs_fit_diagnosis* diag, gs_status_map* map, uint64_t* ticket);
+/* framework.Code of a status word: 0 Success, 1 Unschedulable, 2 UnschedulableAndUnresolvable (as gs_reason_string) */
+int gs_status_framework_code(uint16_t word);
+/* [upstream] nodesWherePreemptionMightHelp over one row: the nodes whose status is not UnschedulableAndUnresolvable,
+ * ascending, up to cap; returns their count (untruncated). GS_EINVAL for a NULL row, or NULL nodes with cap > 0. */
+int gs_preemption_candidates(const uint16_t* row, uint32_t num_nodes, uint32_t* nodes, uint32_t cap);
+
 /* ---- NodeNUMAResource state ---- */
 /* Register a CPUTopology; returns its id in *id (identical topologies may share one id). */
 int gs_topology_register(gs_ctx* ctx, const gs_cpu_topology* topo, int32_t* id);

@@ -79,6 +79,33 @@ def fit_error_message(diag, scalar_names=None) -> str:
     load().gs_fit_error_string(C.byref(d), names, buf, len(buf))
     return buf.value.decode()
 
+
+def status_code(word: int) -> int:
+    """GS_STATUS_CODE: the GS_FAIL_* bits of a status word (what reason_string takes)."""
+    return int(word) & 0x0FFF
+
+
+def status_scalar_mask(word: int) -> int:
+    """GS_STATUS_SCALAR_MASK: the scalar_mask of a status word, exactly the resource slots 3..6 that were short."""
+    return ((int(word) >> 12) & 0xF) << 3
+
+
+def status_framework_code(word: int) -> int:
+    """gs_status_framework_code: 0 Success, 1 Unschedulable, 2 UnschedulableAndUnresolvable."""
+    return load().gs_status_framework_code(int(word))
+
+
+def preemption_candidates(row, cap: int | None = None) -> tuple[int, np.ndarray]:
+    """gs_preemption_candidates over one status row: (count, the first min(count, cap) nodes, ascending)."""
+    row = np.ascontiguousarray(row, dtype=np.uint16)
+    cap = len(row) if cap is None else int(cap)
+    nodes = np.zeros(max(cap, 1), np.uint32)
+    n = load().gs_preemption_candidates(ptr(row), len(row), ptr(nodes), cap)
+    if n < 0:
+        raise ValueError(f"gs_preemption_candidates: {n}")
+    return n, nodes[:min(n, cap)]
+
+
 GS_FAIL_FIT_PODS, GS_FAIL_FIT_CPU, GS_FAIL_FIT_MEMORY = 0x01, 0x02, 0x04
 GS_FAIL_FIT_EPHEMERAL, GS_FAIL_FIT_SCALAR, GS_FAIL_LOADAWARE = 0x08, 0x10, 0x20
 GS_PLACED_SLOWPATH = 0x1
@@ -199,6 +226,12 @@ class GsPlacement(C.Structure):
 class GsFitDiagnosis(C.Structure):
     _fields_ = [("valid", u32), ("num_all_nodes", u32), ("failed_nodes", u32), ("unresolvable_nodes", u32),
                 ("reasons", u32 * 24)]
+
+
+class GsStatusMap(C.Structure):
+    """gs_status_map: the per-node status rows of a call's FitError pods (gs_schedule_diag_nodes)."""
+    _fields_ = [("words", C.c_void_p), ("cap_rows", u32), ("row_of", C.c_void_p), ("rows_used", u32),
+                ("rows_dropped", u32)]
 
 
 class GsStats(C.Structure):
@@ -335,7 +368,7 @@ STRUCT_SIZES = {
     "gs_numa_args": C.sizeof(GsNumaArgs), "gs_quota_group": C.sizeof(GsQuotaGroup),
     "gs_quota_status": C.sizeof(GsQuotaStatus), "gs_node_devices": C.sizeof(GsNodeDevices),
     "gs_reservation": C.sizeof(GsReservation), "gs_pod_ext": C.sizeof(GsPodExt), "gs_ext_args": C.sizeof(GsExtArgs),
-    "gs_ext_placement": C.sizeof(GsExtPlacement),
+    "gs_ext_placement": C.sizeof(GsExtPlacement), "gs_status_map": C.sizeof(GsStatusMap),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -364,6 +397,10 @@ SIGNATURES = {
     "gs_schedule_diag": (C.c_int, [P, P, u32, P, P, P]),
     "gs_schedule_submit_diag": (C.c_int, [P, P, u32, P, P, P, C.POINTER(u64)]),
     "gs_fit_error_string": (C.c_int, [P, P, C.c_char_p, C.c_size_t]),
+    "gs_schedule_diag_nodes": (C.c_int, [P, P, u32, P, P, P, C.POINTER(GsStatusMap)]),
+    "gs_schedule_submit_diag_nodes": (C.c_int, [P, P, u32, P, P, P, C.POINTER(GsStatusMap), C.POINTER(u64)]),
+    "gs_status_framework_code": (C.c_int, [C.c_uint16]),
+    "gs_preemption_candidates": (C.c_int, [P, u32, P, u32]),
     "gs_comm_unique_id": (C.c_int, [P]),
     "gs_comm_init_rccl": (C.c_int, [P, P, C.c_int, C.c_int]),
     "gs_comm_init_callback": (C.c_int, [P, C.c_int, C.c_int, ALLGATHER_FN, P]),

@@ -112,6 +112,15 @@ struct Slot {
   DevBuf<int32_t> dgl_i32;
   DevBuf<uint32_t> d_ldiag;
   PinnedBuf<uint32_t> h_ldiag;
+  // the diagnosis' status map (gs_schedule_diag_nodes; allocated by the context's first such run, alloc_map)
+  bool map_on = false;              // the slot's batch runs the wide pass's MAP instantiation
+  DevBuf<uint16_t> d_words;         // [MAX_BATCH][npad]: row f = the batch's f-th pod with no node, in queue order
+  PinnedBuf<uint16_t> h_words;      // the rows the host asked for (fetch_rows), same stride
+  int rows_fetched = 0;             // rows of the slot's batch on their way to h_words (fetch_rows -> apply_batch)
+  Event ev_rows;                    // ... the copy's end: the slot's next wide pass with rows waits for it
+  bool rows_in_flight = false;      // ev_rows is recorded and no later pass has waited for it yet
+  DevBuf<uint16_t> d_lwords;        // [pod of the landed pass][landed node]: the landed pass's words
+  PinnedBuf<uint16_t> h_lwords;
 };
 
 }  // namespace
@@ -123,6 +132,7 @@ struct AsyncRun {
   std::vector<uint64_t> seq;
   gs_placement* out = nullptr;
   gs_fit_diagnosis* diag = nullptr;   // gs_schedule_submit_diag
+  gs_status_map* map = nullptr;       // gs_schedule_submit_diag_nodes
   uint64_t ticket = 0;
   int rc = 1;   // 1: not complete
   std::string err;
@@ -269,6 +279,7 @@ struct gs_ctx {
   // ... and of the FitError diagnosis: deriving the landed-row versions, the landed pass (upload to counters, waited for)
   double hd_derive = 0, hd_landed = 0;
   uint64_t hd_batches = 0, hd_versions = 0, hd_pods = 0;
+  uint64_t hd_map_rows = 0, hd_map_bytes = 0;   // status map: rows read back, and their bytes with the landed words'
   // ... and of gs_schedule_ext: per extension pod (records, flushes, the device chain up to the host's wake-up, the
   // Reserves) and per plain run (the whole gs_schedule call)
   double hx_prep = 0, hx_flush = 0, hx_gpu = 0, hx_reserve = 0, hx_plain = 0;
@@ -1372,8 +1383,30 @@ int alloc_diag(gs_ctx* c) {
   return GS_OK;
 }
 
-DiagArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
-  DiagArgs a{};
+// the buffers of the status map, on the context's first run that asks for one (after alloc_diag)
+int alloc_map(gs_ctx* c) {
+  if (c->slot[0].d_words) return GS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const size_t rows = sizeof(uint16_t) * MAX_BATCH * (size_t)c->npad, lw = sizeof(uint16_t) * MAX_BATCH * MAX_BATCH;
+  for (Slot& s : c->slot) {
+    HIP_TRY(c, s.ev_rows.create(hipEventDisableTiming));
+    HIP_TRY(c, s.h_words.alloc(rows));
+    HIP_TRY(c, s.d_lwords.alloc(lw));
+    HIP_TRY(c, s.h_lwords.alloc(lw));
+    HIP_TRY(c, s.d_words.alloc(rows));
+    // the rows start out zeroed, and the read-back path (fetch_rows: copy, event) has run once before a batch is in
+    // flight: its first use costs the host milliseconds, which between two batches would delay the next launch
+    HIP_TRY(c, hipMemsetAsync(s.d_words.get(), 0, rows, c->st_dg.get()));
+    HIP_TRY(c, hipMemcpyAsync(s.h_words.get(), s.d_words.get(), rows, hipMemcpyDeviceToHost, c->st_dg.get()));
+    HIP_TRY(c, hipEventRecord(s.ev_rows.get(), c->st_dg.get()));
+  }
+  HIP_TRY(c, host_wait_stream(c->st_dg.get()));
+  HIP_TRY(c, preload_fit_diag_map());
+  return GS_OK;
+}
+
+DiagMapArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
+  DiagMapArgs a{};
   a.m = c->mv;
   a.pods = s.d_pods.get();
   a.pf = c->pf;
@@ -1384,13 +1417,21 @@ DiagArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
   a.diag = s.d_diag.get();
   a.numa_idx = c->d_numa_idx.get();   // (one rank: the list covers every node)
   a.numa_n = c->numa_on ? c->numa_n : 0;
+  a.words = s.d_words.get();
+  a.npad = c->npad;
   return a;
+}
+
+// the wide pass of slot s's batch: the counters, and with s.map_on each counted pair's status word
+hipError_t launch_wide_pass(const Slot& s, const DiagMapArgs& a, hipStream_t st) {
+  return s.map_on ? launch_fit_diag_map(a, st) : launch_fit_diag(a, st);
 }
 
 // The landed pass of a batch (blocking; off the commit stream): nv row versions staged at the head of s.h_dgl are
 // scattered into the slot's slab with their LoadAware verdicts at `now`, pod f (fpods[f]) is evaluated on versions
-// vidx[f * nL ..], and the nF pods' counters arrive in s.h_ldiag.
-int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL) {
+// vidx[f * nL ..], and the nF pods' counters arrive in s.h_ldiag; map: their status words [f][nL] in s.h_lwords too.
+int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL,
+                bool map) {
   const int nF = (int)fpods.size();
   const size_t off_idx = (size_t)nv * ROW_WORDS * 8;
   const size_t off_pods = (off_idx + (size_t)nv * 4 + 7) & ~(size_t)7;
@@ -1411,8 +1452,15 @@ int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, co
   HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
   HIP_TRY(c, launch_scatter_rows(slab, reinterpret_cast<const uint32_t*>(d + off_idx), reinterpret_cast<const int64_t*>(d),
                                  (uint32_t)nv, st, &sp));
-  HIP_TRY(c, launch_fit_diag_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
-                                    reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(), st));
+  if (map) {
+    HIP_TRY(c, launch_fit_diag_landed_map(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
+                                          reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(),
+                                          s.d_lwords.get(), st));
+    HIP_TRY(c, hipMemcpyAsync(s.h_lwords.get(), s.d_lwords.get(), sizeof(uint16_t) * nF * nL, hipMemcpyDeviceToHost, st));
+  } else {
+    HIP_TRY(c, launch_fit_diag_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
+                                      reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(), st));
+  }
   HIP_TRY(c, hipMemcpyAsync(s.h_ldiag.get(), s.d_ldiag.get(), sizeof(uint32_t) * DIAG_WORDS * nF, hipMemcpyDeviceToHost, st));
   Where w_(c, "diag_landed: the landed pass");
   HIP_TRY(c, host_wait_stream(st));
@@ -1424,8 +1472,10 @@ int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, co
 // prev_b pods (prev: its committed words, prev_out: its placements): its eval pass runs beside that batch's commit, on
 // the mirror as it was before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel);
 // its commit kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
-// diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements.
-int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0, bool diag = false) {
+// diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements; map: the
+// pass also leaves the status rows in the slot's d_words (fetch_rows reads back the ones the caller has room for).
+int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0, bool diag = false,
+                 bool map = false) {
   const int32_t* prev = before ? before->d_committed.get() : nullptr;
   const PlacementDev* prev_out = before ? before->d_out : nullptr;
   const hipStream_t st = c->st.get(), st_ev = c->st_ev.get();
@@ -1557,9 +1607,14 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
   if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
   if (rb != st) HIP_TRY(c, hipStreamWaitEvent(rb, s.ev[4].get(), 0));
   s.diag_on = diag;
+  s.map_on = diag && map;
+  if (s.map_on && s.rows_in_flight) {   // the rows of the slot's last batch are still being read back (fetch_rows)
+    HIP_TRY(c, hipStreamWaitEvent(st, s.ev_rows.get(), 0));
+    s.rows_in_flight = false;
+  }
   if (diag) {   // behind the commit's write-back, before the next batch's fix-up and commit (stream order)
     HIP_TRY(c, hipMemsetAsync(s.d_diag.get(), 0, DIAG_BYTES, st));
-    HIP_TRY(c, launch_fit_diag(diag_args(c, s, b), st));
+    HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));
     if (rb != st) {
       HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
       HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
@@ -1641,9 +1696,9 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     if (M < 0) {
       s.h_out[0] = PlacementDev{-1, (uint32_t)F, 0, 0, GS_PLACED_SLOWPATH, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
       if (s.diag_on) {   // a FitError the host found: nothing landed in the pass, every node from the mirror
-        DiagArgs da = diag_args(c, s, b);
+        DiagMapArgs da = diag_args(c, s, b);
         da.force0 = 1;
-        HIP_TRY(c, launch_fit_diag(da, st));
+        HIP_TRY(c, launch_wide_pass(s, da, st));
         HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS, hipMemcpyDeviceToHost, st));
         HIP_TRY(c, host_wait_stream(st));
       }
@@ -1681,7 +1736,7 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     HIP_TRY(c, hipEventRecord(s.ev[3].get(), st));
     HIP_TRY(c, launch_commit(a, st));
     HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
-    if (s.diag_on) HIP_TRY(c, launch_fit_diag(diag_args(c, s, b), st));   // (the first pass committed nothing: counters 0)
+    if (s.diag_on) HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));   // (the first pass committed nothing: counters 0)
     HIP_TRY(c, hipMemcpyAsync(h_committed, s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
     c->stats.commit_ms += ev_ms(s.ev[3].get(), s.ev[4].get());
@@ -2214,7 +2269,8 @@ void gs_abi_sizes(uint64_t* out, uint32_t n) {
                         sizeof(gs_config), sizeof(gs_placement), sizeof(gs_stats), sizeof(gs_loadaware_args),
                         sizeof(gs_cpu_topology), sizeof(gs_node_numa), sizeof(gs_pod_allocation), sizeof(gs_numa_args),
                         sizeof(gs_quota_group), sizeof(gs_quota_status), sizeof(gs_node_devices),
-                        sizeof(gs_reservation), sizeof(gs_pod_ext), sizeof(gs_ext_args), sizeof(gs_ext_placement)};
+                        sizeof(gs_reservation), sizeof(gs_pod_ext), sizeof(gs_ext_args), sizeof(gs_ext_placement),
+                        sizeof(gs_status_map)};
   for (uint32_t i = 0; i < n && i < sizeof(s) / sizeof(s[0]); ++i) out[i] = s[i];
 }
 
@@ -2425,6 +2481,9 @@ void report_host_timing(const gs_ctx* c) {
             "landed-row versions): deriving the versions %.1f | landed pass, upload to counters %.1f\n",
             (unsigned long long)c->hd_batches, (unsigned long long)c->hd_pods, (unsigned long long)c->hd_versions,
             c->hd_derive / n, c->hd_landed / n);
+    if (c->hd_map_rows)
+      fprintf(stderr, "gpuscore status map: %llu rows read back, %.0f bytes device-to-host per such batch\n",
+              (unsigned long long)c->hd_map_rows, (double)c->hd_map_bytes / n);
   }
 }
 
@@ -2788,6 +2847,9 @@ struct PodRun {
   uint32_t n = 0;
   void* tag = nullptr;
   gs_fit_diagnosis* diag = nullptr;   // gs_schedule_diag: the FitError diagnosis of each pod (else none is computed)
+  gs_status_map* map = nullptr;       // gs_schedule_diag_nodes: the per-node status rows of those pods (with diag)
+  // whether the run's batches run the wide pass with the status rows (a map without rows keeps the counters-only kernels)
+  bool wants_rows() const { return map && map->cap_rows; }
 };
 
 // Several ranks: whether the next run is already known (gs_schedule_submit) is a matter of each rank's timing. The
@@ -2829,6 +2891,11 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
   // device-format rows of the batch's landed nodes are derived there (derive_row / derive_row_numa, the two
   // gs_debug_mirror_check holds to the device's rows) — a row changes only at a landing, so each version is derived
   // once and the pod gets an index per landed node — and evaluated by the landed pass on slot sl's buffers.
+  // mp != nullptr (with dg): the run's status map, the batch's pods being its pods [base, base + n). The batch's pods
+  // with no node take the map's next rows in queue order while rows are left; their device rows (the wide pass wrote
+  // row f for the batch's f-th such pod) are on their way to sl->h_words (fetch_rows, right after the batch was waited
+  // for, on the landed pass's stream), the landed pass's words are patched in at the landed nodes, and each row goes
+  // to the caller's words at its stride of num_nodes.
   std::vector<uint32_t> dg_nodes;
   std::vector<uint16_t> dg_cur, dg_vidx;
   std::vector<uint8_t> dg_stale;
@@ -2836,8 +2903,10 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
   std::vector<int> dg_k;
   auto apply_batch = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
                          bool special, gs_fit_diagnosis* dg = nullptr, const uint32_t* wide = nullptr,
-                         Slot* sl = nullptr) -> int {
-    int nfit = 0, nv = 0;
+                         Slot* sl = nullptr, gs_status_map* mp = nullptr, uint32_t base = 0) -> int {
+    int nfit = 0, nv = 0, nrow = 0;
+    if (mp)
+      for (int k = 0; k < n; ++k) mp->row_of[base + k] = -1;
     if (dg) {
       std::memset(dg, 0, sizeof(gs_fit_diagnosis) * n);
       dg_nodes.clear();
@@ -2847,6 +2916,11 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
           dg_nodes.push_back((uint32_t)hout[k].node);
       }
       if (!nfit) dg = nullptr;
+    }
+    if (dg && mp) {
+      nrow = (int)std::min<uint32_t>((uint32_t)nfit, mp->cap_rows - mp->rows_used);
+      mp->rows_dropped += (uint32_t)(nfit - nrow);
+      if (nrow != sl->rows_fetched) return fail(c, GS_ESTATE, "status map: the batch's rows were not read back");
     }
     const int nL = dg ? (int)dg_nodes.size() : 0;
     if (dg) {
@@ -2890,8 +2964,20 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     }
     if (!dg) return GS_OK;
     const int64_t t1 = c->host_timing ? mono_ns() : 0;
-    if (nL)
-      if (int rc = diag_landed(c, *sl, nv, dg_pods, dg_vidx, nL)) return rc;
+    if (nL) {
+      if (int rc = diag_landed(c, *sl, nv, dg_pods, dg_vidx, nL, nrow > 0)) return rc;
+    } else if (nrow) {
+      Where w_(c, "apply_batch: the status rows");
+      HIP_TRY(c, host_wait_stream(c->st_dg.get()));
+    }
+    for (int f = 0; f < nrow; ++f) {   // (dg_k is in queue order: its first nrow pods hold the rows)
+      const uint32_t row = mp->rows_used + (uint32_t)f;
+      uint16_t* dst = mp->words + (size_t)row * c->N;
+      std::memcpy(dst, sl->h_words.get() + (size_t)f * c->npad, sizeof(uint16_t) * c->N);
+      for (int j = 0; j < nL; ++j) dst[dg_nodes[j]] = sl->h_lwords.get()[(size_t)f * nL + j];
+      mp->row_of[base + dg_k[f]] = (int32_t)row;
+    }
+    if (mp) mp->rows_used += (uint32_t)nrow;
     const uint32_t* landed = sl->h_ldiag.get();
     for (size_t f = 0; f < dg_k.size(); ++f) {
       const int k = dg_k[f];
@@ -2910,6 +2996,8 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       c->hd_batches += 1;
       c->hd_versions += nv;
       c->hd_pods += dg_k.size();
+      c->hd_map_rows += (uint64_t)nrow;
+      if (nrow) c->hd_map_bytes += sizeof(uint16_t) * ((size_t)nrow * c->npad + (size_t)dg_k.size() * nL);
     }
     return GS_OK;
   };
@@ -2924,15 +3012,37 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     bool active = false;
     gs_fit_diagnosis* diag = nullptr;
     Slot* slot = nullptr;   // the slot the batch ran on (its landed-pass buffers)
+    gs_status_map* map = nullptr;
+    uint32_t base = 0;
   } pend;
   std::vector<PlacementDev> pend_out;
   std::vector<PodVec> pend_pods;
   std::vector<uint32_t> pend_wide;
+  // The status rows of slot sl's batch, just waited for (n committed pods, placements hout), into sl->h_words: the
+  // batch's share of the map's rows is chosen here (every batch before it is applied: rows_used is current), and
+  // those rows alone are copied, as one block (rows are in queue order), on the landed pass's stream. The batch may be
+  // applied deferred, after the batch two ahead is launched into this slot: that batch's wide pass waits for the copy
+  // on the device (launch_batch), so the launch is not held back and the rows are not overwritten under the copy.
+  auto fetch_rows = [&](Slot& sl, const PlacementDev* hout, int n, gs_status_map* mp) -> int {
+    sl.rows_fetched = 0;
+    if (!mp || mp->rows_used >= mp->cap_rows) return GS_OK;
+    uint32_t nfit = 0;
+    for (int k = 0; k < n; ++k) nfit += hout[k].node < 0;
+    const uint32_t nrow = std::min<uint32_t>(nfit, mp->cap_rows - mp->rows_used);
+    if (!nrow) return GS_OK;
+    if (!sl.map_on) return fail(c, GS_ESTATE, "status map: the batch ran without its rows");
+    HIP_TRY(c, hipMemcpyAsync(sl.h_words.get(), sl.d_words.get(), sizeof(uint16_t) * (size_t)nrow * c->npad,
+                              hipMemcpyDeviceToHost, c->st_dg.get()));
+    HIP_TRY(c, hipEventRecord(sl.ev_rows.get(), c->st_dg.get()));
+    sl.rows_in_flight = true;
+    sl.rows_fetched = (int)nrow;
+    return GS_OK;
+  };
   auto apply_pending = [&]() -> int {
     if (!pend.active) return GS_OK;
     pend.active = false;
     return apply_batch(pend.pods, pend.out, pend.n, pend_out.data(), pend_pods.data(), false, pend.diag,
-                       pend_wide.data(), pend.slot);
+                       pend_wide.data(), pend.slot, pend.map, pend.base);
   };
   auto body = [&]() -> int {
     int rc = GS_OK;
@@ -2961,7 +3071,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         cur_b = batch_len(c, pods, i, run.n, &cur_special);
         // (a cpuset pod whose node is outside the device cpuset scope ends the batch inside the commit kernel)
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows()))) return rc;
       }
       // the batch after this one: in this run, or the first of the next run
       const gs_pod* np = nullptr;
@@ -2969,13 +3079,14 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       uint32_t nj = 0, nn = 0;
       const uint32_t j = i + cur_b;
       bool ndiag = run.diag != nullptr;   // whether the batch after this one is diagnosed (its own run's choice)
+      bool nmap = run.wants_rows();
       if (j < run.n) {
         np = pods; ns = run.seq; nj = j; nn = run.n;
       } else {
         if (!have_nxt) have_nxt = next_run(&nxt);
         bool use = have_nxt && nxt.n;
         if (c->nranks > 1 && (rc = agree_next_run(c, &use))) { drain(); return rc; }
-        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; }
+        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; nmap = nxt.wants_rows(); }
       }
       bool spec = false;
       int nb = 0;
@@ -2992,7 +3103,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         if (!sf && !uid_overlap(pods + i, cur_b, np + nj, nb)) {
           rc = stage_batch(c, ahead, np, ns, nj, nb, true);
           const auto t_b = hclk::now();
-          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag);
+          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag, nmap);
           if (c->host_timing) {
             const double st = std::chrono::duration<double, std::micro>(t_b - t_a).count();
             const double la = std::chrono::duration<double, std::micro>(hclk::now() - t_b).count();
@@ -3015,7 +3126,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         drain();
         if ((rc = apply_pending())) return rc;
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows()))) return rc;
         inflight = true;
         spec_ok = false;
         continue;
@@ -3024,6 +3135,10 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       const PodVec* h_pods = cur.h_pods.get();
       // the device-side continuation flag the speculative pass read
       const bool host_work = cur.h_committed.get()[1] != 1;
+      if ((rc = fetch_rows(cur, cur.h_out, committed, run.map))) {
+        if (spec) drain();
+        return rc;
+      }
       if (spec && !host_work && !cur_special && committed == cur_b) {
         // no host row changes: keep the results (this slot's buffers are reused by the batch two ahead) and apply them
         // after that batch is launched
@@ -3035,9 +3150,11 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         pend.active = true;
         pend.diag = run.diag ? run.diag + i : nullptr;
         pend.slot = &cur;
+        pend.map = run.map;
+        pend.base = i;
         if (run.diag) pend_wide.assign(cur.h_diag.get(), cur.h_diag.get() + (size_t)DIAG_WORDS * committed);
       } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special,
-                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur))) {
+                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur, run.map, i))) {
         if (spec) drain();
         return rc;
       }
@@ -3106,6 +3223,7 @@ void async_worker(gs_ctx* c) {
       p.seq = r->seq.data();
       p.out = r->out;
       p.diag = r->diag;
+      p.map = r->map;
       p.n = (uint32_t)r->pods.size();
       p.tag = r.get();
       return p;
@@ -3173,7 +3291,7 @@ int diag_supported(gs_ctx* c) {
 }
 
 int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                 gs_fit_diagnosis* diag) {
+                 gs_fit_diagnosis* diag, gs_status_map* map = nullptr) {
   int rc = ready(c);
   if (rc) return rc;
   for (uint32_t i = 0; i < npods; ++i)
@@ -3184,12 +3302,13 @@ int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* 
   run.out = out;
   run.n = npods;
   run.diag = diag;
+  run.map = map;
   return schedule_stream(c, run, [](PodRun*) { return false; }, [](const PodRun&, int) {});
 }
 
 // gs_schedule_submit: the run copied and queued for the worker
 int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-               gs_fit_diagnosis* diag, uint64_t* ticket) {
+               gs_fit_diagnosis* diag, uint64_t* ticket, gs_status_map* map = nullptr) {
   auto r = std::make_shared<AsyncRun>();
   // checks that write nothing (the worker may be running): on an error, wait for it, then report
   if (c->n_valid != c->N) {
@@ -3209,6 +3328,7 @@ int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* se
   for (uint32_t i = 0; i < npods; ++i) r->seq[i] = seq ? seq[i] : (uint64_t)i;
   r->out = out;
   r->diag = diag;
+  r->map = map;
   if (!c->aq) {
     c->aq = std::make_unique<AsyncQueue>();
     c->aq->th = std::thread(async_worker, c);
@@ -3256,6 +3376,56 @@ int gs_schedule_submit_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const
     if (int rc = alloc_diag(c)) return rc;
   }
   return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket);
+}
+
+namespace {
+// the caller's status map before a run: no rows handed out (row_of is written per batch, as out is)
+bool map_begin(gs_status_map* m, uint32_t npods) {
+  if (!m || (npods && !m->row_of) || (m->cap_rows && !m->words)) return false;
+  m->rows_used = m->rows_dropped = 0;
+  return true;
+}
+}  // namespace
+
+int gs_schedule_diag_nodes(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                           gs_fit_diagnosis* diag, gs_status_map* map) {
+  if (!c || (npods && (!pods || !out || !diag)) || !map_begin(map, npods)) return GS_EINVAL;
+  quiesce(c);
+  if (int rc = diag_supported(c)) return rc;
+  if (int rc = alloc_diag(c)) return rc;
+  if (int rc = alloc_map(c)) return rc;
+  return schedule_run(c, pods, npods, seq, out, npods ? diag : nullptr, npods ? map : nullptr);
+}
+
+int gs_schedule_submit_diag_nodes(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                                  gs_fit_diagnosis* diag, gs_status_map* map, uint64_t* ticket) {
+  if (!c || !ticket || (npods && (!pods || !out || !diag)) || !map_begin(map, npods)) return GS_EINVAL;
+  if (c->nranks > 1 || c->window_k || !c->st_dg || !c->slot[0].d_words) {
+    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
+    if (int rc = diag_supported(c)) return rc;
+    if (int rc = alloc_diag(c)) return rc;
+    if (int rc = alloc_map(c)) return rc;
+  }
+  return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket, npods ? map : nullptr);
+}
+
+int gs_status_framework_code(uint16_t word) { return gs_reason_string(GS_STATUS_CODE(word), 0, nullptr, nullptr, 0); }
+
+int gs_preemption_candidates(const uint16_t* row, uint32_t num_nodes, uint32_t* nodes, uint32_t cap) {
+  if (!row || (cap && !nodes)) return GS_EINVAL;
+  uint32_t n = 0;
+  uint16_t last = 0;   // (a row holds few distinct words, mostly in runs: the last word's code is kept)
+  int last_code = 0;
+  for (uint32_t i = 0; i < num_nodes; ++i) {
+    if (row[i] != last) {
+      last = row[i];
+      last_code = gs_status_framework_code(last);
+    }
+    if (last_code == 2) continue;
+    if (n < cap) nodes[n] = i;
+    ++n;
+  }
+  return (int)n;
 }
 
 int gs_schedule_wait(gs_ctx* c, uint64_t ticket) {

@@ -250,11 +250,27 @@ struct DiagArgs {
 // batch's committed pods did not land on is evaluated (the mirror holds its state at the pod's turn) and its failure
 // reasons are added to the pod's counters. Does nothing for a voided pass or a batch without such a pod.
 hipError_t launch_fit_diag(const DiagArgs& a, hipStream_t st);
+// ---- the status map of the diagnosis (gs_schedule_diag_nodes) ----
+// One status word per (FitError pod, node): the GS_FAIL_* bits of the first failing plugin (bits 0..11) and, with
+// GS_FAIL_FIT_SCALAR, the short resource slots 3..6 in bits 12..15 (gpuscore.h GS_STATUS_CODE / _SCALAR_MASK).
+struct DiagMapArgs : DiagArgs {
+  uint16_t* words;           // [row][npad]; row: the pod's rank among the pass's committed pods with node < 0, in
+                             // queue order (what the host counts from the placements)
+  uint32_t npad;
+};
+// launch_fit_diag, and the status word of every pair it counts stored at words[row][node]: entries of the batch's
+// landed nodes and of the padding are left as they were.
+hipError_t launch_fit_diag_map(const DiagMapArgs& a, hipStream_t st);
 // The landed rows: block f evaluates pod f (pods[f]) on the nL row versions vidx[f * nL ..] of the slab (host-derived
 // rows of the batch's landed nodes as they were at the pod's turn) and writes the pod's counters to out[f].
 // Reads the slab only.
 hipError_t launch_fit_diag_landed(const MirrorView& slab, const PodVec* pods, const Profile& pf, const uint16_t* vidx,
                                   int nF, int nL, uint32_t* out, hipStream_t st);
+// Loads the map kernels' code (a kernel's first launch otherwise does, on the host's time between two batches).
+hipError_t preload_fit_diag_map();
+// launch_fit_diag_landed, and the status words of pod f on its nL versions at words[f * nL ..].
+hipError_t launch_fit_diag_landed_map(const MirrorView& slab, const PodVec* pods, const Profile& pf, const uint16_t* vidx,
+                                      int nF, int nL, uint32_t* out, uint16_t* words, hipStream_t st);
 
 int64_t host_tiebreak_position(uint64_t seed, uint64_t seq, int64_t T);
 // diagnostics (gs_probe.hip): cycles of one pair evaluation as the commit kernel runs it

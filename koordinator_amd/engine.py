@@ -149,10 +149,53 @@ class Engine:
         return (t.value, out)
 
     def schedule_wait(self, handle):
-        """The placements of a schedule_submit handle; (placements, diag) of a schedule_submit_diag handle."""
+        """The placements of a schedule_submit handle; (placements, diag) of a schedule_submit_diag handle;
+        (placements, diag, words, row_of) of a schedule_submit_diag_nodes handle."""
         t, *res = handle
         self._chk(lib().gs_schedule_wait(self._h, t), "gs_schedule_wait")
+        if res and isinstance(res[-1], abi.GsStatusMap):   # words: the rows handed out
+            m = res.pop()
+            res[2] = res[2][:m.rows_used]
         return res[0] if len(res) == 1 else tuple(res)
+
+    def _status_map(self, pods, cap_rows):
+        """The caller-owned buffers of a gs_status_map; cap_rows None: a row for every pod."""
+        cap = len(pods) if cap_rows is None else int(cap_rows)
+        words = np.zeros((cap, self.cfg.num_nodes), np.uint16)
+        row_of = np.full(len(pods), -1, np.int32)
+        m = abi.GsStatusMap(words=abi.ptr(words) if cap else None, cap_rows=cap, row_of=abi.ptr(row_of))
+        return words, row_of, m
+
+    def schedule_diag_nodes(self, pods, seq=None, cap_rows=None):
+        """gs_schedule_diag_nodes: (placements, diag, words, row_of). words[row_of[i]] (uint16[num_nodes]) is the
+        Filter status of every node at the turn of pod i, a pod with node -1 (abi.status_code / status_scalar_mask /
+        status_framework_code / preemption_candidates read it); row_of[i] is -1 for a placed pod and for a FitError
+        pod beyond the first cap_rows of them (None: a row for every pod). words holds the rows handed out."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        diag = np.zeros(len(pods), abi.FIT_DIAGNOSIS_DTYPE)
+        words, row_of, m = self._status_map(pods, cap_rows)
+        self._chk(lib().gs_schedule_diag_nodes(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out),
+                                               abi.ptr(diag), C.byref(m)), "gs_schedule_diag_nodes")
+        return out, diag, words[:m.rows_used], row_of
+
+    def schedule_submit_diag_nodes(self, pods, seq=None, cap_rows=None):
+        """gs_schedule_submit_diag_nodes: a handle for schedule_wait, which then returns what schedule_diag_nodes does."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        diag = np.zeros(len(pods), abi.FIT_DIAGNOSIS_DTYPE)
+        words, row_of, m = self._status_map(pods, cap_rows)
+        t = C.c_uint64(0)
+        self._chk(lib().gs_schedule_submit_diag_nodes(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out),
+                                                      abi.ptr(diag), C.byref(m), C.byref(t)),
+                  "gs_schedule_submit_diag_nodes")
+        return (t.value, out, diag, words, row_of, m)
 
     def schedule_diag(self, pods, seq=None):
         """gs_schedule_diag: (placements, diag); diag[i] (abi.FIT_DIAGNOSIS_DTYPE) is the FitError diagnosis of a pod

@@ -7,7 +7,11 @@ Prints one JSON line. Run: python scripts/bench_fit_diag.py [--steps 20]
                   per batch spent deriving landed-row versions and in the landed pass
   --only V        run variant V (as_is | every17) diagnosed only, for a profiler:
                   rocprofv3 --kernel-trace --stats -d OUT -- python scripts/bench_fit_diag.py --only every17 --steps 5
-                  (fit_diag_kernel<...> and fit_diag_landed_kernel are the diagnosis' kernels)"""
+                  (fit_diag_kernel<...> and fit_diag_landed_kernel are the diagnosis' kernels)
+  --nodes-map     a third run per variant through gs_schedule_submit_diag_nodes, with a status row for every FitError pod
+                  of a step (cap_rows = pods per step): its pods/s, the rows and their device-to-host bytes, and the
+                  ratio to the counters-only run beside it; with --only, the diagnosed run is that one
+                  (fit_diag_kernel<..., true> and fit_diag_landed_map_kernel are its kernels)"""
 import argparse
 import json
 import os
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-timing", action="store_true")
     ap.add_argument("--only", choices=["as_is", "every17"], default=None)
+    ap.add_argument("--nodes-map", action="store_true")
     args = ap.parse_args()
 
     from koordinator_amd import abi, config, synth
@@ -42,11 +47,16 @@ def main():
     big["request_mask"][5::17] |= 1
     variants = {"as_is": cluster.pods, "every17": big}
 
-    def run(pods, diag: bool):
+    npad = (args.nodes + 1023) // 1024 * 1024   # the device rows' stride
+
+    def run(pods, diag: bool, nodes_map: bool = False):
         eng = Engine(cfg)
         synth.load_into(eng, cluster)
         submit = eng.schedule_submit_diag if diag else eng.schedule_submit
+        if nodes_map:
+            submit = lambda p, q: eng.schedule_submit_diag_nodes(p, q, cap_rows=P)
         first = (lambda r: r[0]) if diag else (lambda r: r)
+        rows = 0
         for w in range(args.warmup):
             eng.schedule_wait(submit(pods[w * P:(w + 1) * P], seq[w * P:(w + 1) * P]))
         eng.synchronize()
@@ -61,28 +71,37 @@ def main():
             if diag:
                 diagnosed += int(r[1]["valid"].sum())
                 assert (r[1]["failed_nodes"][r[1]["valid"] == 1] == args.nodes).all()
+            if nodes_map:   # a row for every such pod, in queue order, no entry without a status
+                assert np.array_equal(np.nonzero(r[3] >= 0)[0], np.nonzero(r[1]["valid"])[0]) and (r[2] != 0).all()
+                rows += len(r[2])
             h = h2
         eng.synchronize()
         dt = time.perf_counter() - t0
         bad = eng.mirror_check()
         eng.close()
         assert bad == 0 and (not diag or diagnosed == unplaced)
-        return {"pods_per_s": round(args.steps * P / dt, 1), "fit_errors": unplaced}
+        res = {"pods_per_s": round(args.steps * P / dt, 1), "fit_errors": unplaced}
+        if nodes_map:   # (the landed pass's words, at most 32 KiB per batch, are not counted)
+            res.update(rows=rows, d2h_bytes_per_batch=round(rows * npad * 2 / (args.steps * P / 128)))
+        return res
 
     out = {"workload": f"C3 {args.nodes} nodes x {args.steps} steps of {P} pods, submitted one step ahead"}
     for name, pods in variants.items():
         if args.only and name != args.only:
             continue
         if args.only:
-            out[name] = {"diag": run(pods, True)}
+            out[name] = {"map" if args.nodes_map else "diag": run(pods, True, args.nodes_map)}
             continue
         plain, diag = run(pods, False), run(pods, True)
         out[name] = {"plain": plain, "diag": diag,
                      "diag_over_plain": round(diag["pods_per_s"] / plain["pods_per_s"], 4)}
+        if args.nodes_map:
+            out[name]["map"] = run(pods, True, True)
+            out[name]["map_over_diag"] = round(out[name]["map"]["pods_per_s"] / diag["pods_per_s"], 4)
         if args.host_timing:
             os.environ["GS_HOST_TIMING"] = "1"
             print(f"host timing, variant {name}:", file=sys.stderr, flush=True)
-            run(pods, True)
+            run(pods, True, args.nodes_map)
             del os.environ["GS_HOST_TIMING"]
     print(json.dumps(out), flush=True)
 
