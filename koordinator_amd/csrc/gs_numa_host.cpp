@@ -698,8 +698,12 @@ bool numa_allocate_cpuset(const NumaNode& n, int num_cpus, int bind, bool requir
 // maxRefCount 1 or 2 (RefCounts 0-2), exclusivity and reservations, and random requests (bind and exclusive
 // policies, strategies, NUMA splits); after each selection the device state update (td_reserve_update) is compared
 // with the host's re-derivation of the node after addPodAllocation. Returns the number of mismatches; `msg`
-// describes the first one. Test hook, not part of include/gpuscore.h.
-extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t len) {
+// describes the first one.
+// `edges`: the draws of gsx_cpuset_selftest_edges — 1, 2, 4 or 8 sockets with sockets x NUMA nodes per socket <= 8 (every
+// entry of TdPack8, td_go_sort's gap-6 pass from 7 sockets), on the wide shape too, the zones of a node with more than
+// GS_MAX_NUMA NUMA nodes spread to its last one, and requests up to every available CPU + 2 (beyond cpn and cps on
+// every shape). Each of the two draws takes one rnd call as before, so the stream of edges = 0 is unchanged.
+static int cpuset_selftest(uint64_t seed, int iters, bool edges, char* msg, size_t len) {
   using namespace gs;
   uint64_t s = seed;
   auto rnd = [&](int n) {
@@ -719,10 +723,12 @@ extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t l
   static const int kCpc[] = {1, 2, 2, 4};
   for (int it = 0; it < iters; ++it) {
     const bool wide = rnd(3) == 0;
-    int sockets = 1 + rnd(2), nps = 1 + rnd(4), cores_pn = 1 + rnd(6), cpc = kCpc[rnd(4)];
+    int sockets = edges ? 1 << rnd(4) : 1 + rnd(2), nps = 1 + rnd(4), cores_pn = 1 + rnd(6), cpc = kCpc[rnd(4)];
+    if (edges && sockets * nps > TD_NODES) nps = TD_NODES / sockets;
     if (wide) {   // 65-128 cores, SMT 1 / 2 (the C3 shapes: 2 sockets, 2 or 4 NUMA nodes, 32-128 cores)
-      sockets = 2;
+      if (!edges) sockets = 2;
       nps = 1 + rnd(2);
+      if (sockets * nps > TD_NODES) nps = TD_NODES / sockets;
       cpc = 1 + rnd(2);
       const int per = 128 / (sockets * nps);
       cores_pn = per / 2 + 1 + rnd(per / 2);
@@ -754,7 +760,9 @@ extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t l
     const int nnodes = sockets * nps, nz = nnodes < GS_MAX_NUMA ? nnodes : GS_MAX_NUMA;
     n.cfg.num_zones = nz;
     for (int z = 0; z < nz; ++z) {
-      n.cfg.zones[z].node_id = 2 * z + (rnd(8) == 0 ? 1 : 0);   // now and then a zone the topology lacks
+      // (edges: non-adjacent NUMA nodes up to the last one when the topology has more than GS_MAX_NUMA)
+      const int zn = edges && nnodes > nz ? z * (nnodes - 1) / (nz - 1) : z;
+      n.cfg.zones[z].node_id = 2 * zn + (rnd(8) == 0 ? 1 : 0);   // now and then a zone the topology lacks
       n.cfg.zones[z].mask = GS_USAGE_CPU | GS_USAGE_MEMORY;
     }
     const int density = 1 + rnd(4);
@@ -777,7 +785,7 @@ extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t l
     if (cs.topo != 0) { report(it, "cpu state not device-eligible"); continue; }
     const CpuMask avail = numa_available(n);
     const int na = avail.count();
-    const int needed = 1 + rnd(std::max(1, std::min(na + 2, 48)));
+    const int needed = 1 + rnd(std::max(1, edges ? na + 2 : std::min(na + 2, 48)));
     const int bind = rnd(4), ep = rnd(3);
     const char* shape = wide ? "wide" : "compact";
     // takeCPUs over the whole available set
@@ -859,4 +867,55 @@ extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t l
     }
   }
   return bad;
+}
+
+// Test hooks, not part of include/gpuscore.h.
+extern "C" int gsx_cpuset_selftest(uint64_t seed, int iters, char* msg, size_t len) {
+  return cpuset_selftest(seed, iters, false, msg, len);
+}
+extern "C" int gsx_cpuset_selftest_edges(uint64_t seed, int iters, char* msg, size_t len) {
+  return cpuset_selftest(seed, iters, true, msg, len);
+}
+
+// The host restatement of takeCPUs (gs::take_cpus, the judge behind gs_verify_cpusets) on
+// buildCPUTopologyForTest(sockets, nodes_per_socket, cores_per_node, cpus_per_core) (cpu_accumulator_test.go:30-57: dense
+// CPU, core and NUMA node ids), with the arguments of the oracle's or_take_cpus_test: `available` and `result` are
+// GS_CPU_WORDS words, alloc_ref[cpu] >= 0 gives an allocated CPU's RefCount and alloc_excl[cpu] its exclusive policy
+// (either may be NULL). 0: a set was taken; -1: takeCPUs errors; -2: the shape is not a topology of <= GS_MAX_CPUS CPUs.
+extern "C" int gsx_take_cpus_test(int sockets, int nodes_per_socket, int cores_per_node, int cpus_per_core, int max_ref,
+                                  const uint64_t* available, const int32_t* alloc_ref, const int32_t* alloc_excl,
+                                  int needed, int bind, int excl, int strategy, uint64_t* result) {
+  using namespace gs;
+  if (!available || !result || sockets < 1 || nodes_per_socket < 1 || cores_per_node < 1 || cpus_per_core < 1 ||
+      (int64_t)sockets * nodes_per_socket * cores_per_node * cpus_per_core > GS_MAX_CPUS)
+    return -2;
+  gs_cpu_topology in;
+  std::memset(&in, 0, sizeof(in));
+  int cpu = 0, core = 0, node = 0;
+  for (int sk = 0; sk < sockets; ++sk)
+    for (int nn = 0; nn < nodes_per_socket; ++nn, ++node)
+      for (int co = 0; co < cores_per_node; ++co, ++core)
+        for (int th = 0; th < cpus_per_core; ++th, ++cpu) {
+          in.core_id[cpu] = core;
+          in.socket_id[cpu] = (uint8_t)sk;
+          in.node_id[cpu] = (uint8_t)node;
+        }
+  in.num_cpus = cpu;
+  const char* err = nullptr;
+  auto t = make_topo(in, &err);
+  if (!t || !t->valid) return -2;
+  CpuMask avail;
+  uint16_t ref[GS_MAX_CPUS] = {0};
+  uint8_t ex[GS_MAX_CPUS] = {0};
+  for (int c = 0; c < in.num_cpus; ++c) {
+    if ((available[c >> 6] >> (c & 63)) & 1) avail.set(c);
+    if (alloc_ref && alloc_ref[c] >= 0) {
+      ref[c] = (uint16_t)alloc_ref[c];
+      ex[c] = alloc_excl ? (uint8_t)alloc_excl[c] : 0;
+    }
+  }
+  CpuMask out;
+  const bool ok = take_cpus(*t, max_ref, avail, ref, ex, needed, bind, excl, strategy, &out);
+  for (int w = 0; w < GS_CPU_WORDS; ++w) result[w] = ok ? out.w[w] : 0;
+  return ok ? 0 : -1;
 }
