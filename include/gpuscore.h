@@ -810,6 +810,119 @@ int gs_quota_settle_batch(gs_quota_group* groups, uint32_t n, const int64_t* run
                           const int32_t* quota, const int64_t* requests, const uint32_t* request_mask,
                           const uint32_t* flags, uint32_t count, const int32_t* placed_node, gs_quota_status* status);
 
+/* ---- ElasticQuota PostFilter: the preemption dry run ----
+ * Plugin.PostFilter (elasticquota/plugin.go:301-321) runs [upstream] preemption.Evaluator.Preempt with the plugin as
+ * its Interface: PodEligibleToPreemptOthers (elasticquota/preempt.go:61-94), nodesWherePreemptionMightHelp over the
+ * pod's NodeToStatusMap, DryRunPreemption over ALL of those nodes (GetOffsetAndNumCandidates returns (0, nodes),
+ * preempt.go:43-45: no early stop), SelectVictimsOnNode per node (preempt.go:111-215) and pickOneNodeForPreemption.
+ * The Evaluator is not part of the reference tree: parity of its part is unpinned, like selectHost's.
+ *
+ * The resident-pod table: what SelectVictimsOnNode reads of nodeInfo.Pods. It is parallel to the NodeInfo aggregates
+ * of gs_nodes_upsert: it never changes a mirror row, gs_schedule does not insert into it (the binding registers a
+ * placed pod, as it does for podAssignCache), and a pod that is not in it is simply not a potential victim. */
+#define GS_MAX_NODE_PODS 128              /* resident pods per node in the table (two 64-bit victim words) */
+#define GS_RESIDENT_NON_PREEMPTIBLE 0x1u  /* extension.IsPodNonPreemptible(pod) (canPreempt, preempt.go:283-294) */
+#define GS_RESIDENT_QUOTA_TRACKED 0x2u    /* quotaInfo.IsPodExist(pod) of the pod's quota (plugin.go:274,294) */
+#define GS_RESIDENT_TERMINATING 0x4u      /* pod.DeletionTimestamp != nil (preempt.go:84) */
+typedef struct gs_resident_pod {
+  uint64_t uid;
+  int64_t start_time_ns;                  /* [upstream] util.GetPodStartTime; a pod without one: the caller's "now" */
+  int64_t requests[GS_NUM_RES];           /* what NodeInfo.RemovePod subtracts from Requested (the pod's gs_pod.requests) */
+  int64_t quota_request[GS_QUOTA_DIMS];   /* core.PodRequestsAndLimits in the units of gs_quota_* */
+  uint32_t quota_request_mask;            /* its keys */
+  int32_t priority;                       /* corev1helpers.PodPriority */
+  int32_t quota;                          /* integer id of getPodAssociateQuotaName(pod) */
+  uint32_t flags;                         /* GS_RESIDENT_* */
+} gs_resident_pod;
+/* Pod informer handlers of the table. add: pod i joins node node_idx[i]; GS_EUNSUPPORTED for a
+ * 129th pod on a node, GS_EINVAL for a uid the node already holds, a node index out of range or a negative request
+ * (nothing of the call is applied). remove: by uid; a uid the node does not hold is ignored. */
+int gs_node_pods_add(gs_ctx* ctx, const uint32_t* node_idx, const gs_resident_pod* pods, uint32_t n);
+int gs_node_pods_remove(gs_ctx* ctx, const uint32_t* node_idx, const uint64_t* uids, uint32_t n);
+/* The node's pods in MoreImportantPod order ([upstream] util.MoreImportantPod: higher priority first, then the
+ * earlier start time; the reference's sort.Slice is unstable, so a remaining tie is fixed here: ascending uid), up to
+ * cap; returns their count. This is the order the victim bits of gs_preempt_detail index. */
+int gs_node_pods_get(gs_ctx* ctx, uint32_t node, gs_resident_pod* out, uint32_t cap);
+
+#define GS_PREEMPT_NEVER 0x1u             /* pod.Spec.PreemptionPolicy == Never (preempt.go:62-65) */
+typedef struct gs_preemptor {
+  gs_pod pod;
+  int32_t priority;                       /* corev1helpers.PodPriority */
+  int32_t quota;                          /* quota id; -1 = postFilterState.skip (no quota: the quota check passes) */
+  int64_t quota_request[GS_QUOTA_DIMS];   /* core.PodRequestsAndLimits(pod) (preempt.go:173) */
+  uint32_t quota_request_mask;
+  uint32_t limit_mask;                    /* keys of postFilterState.usedLimit */
+  int64_t used[GS_QUOTA_DIMS];            /* postFilterState.used: the quota's used at the pod's PreFilter */
+  int64_t used_limit[GS_QUOTA_DIMS];      /* postFilterState.usedLimit: the Runtime or Max the gate compared with */
+  uint32_t flags;                         /* GS_PREEMPT_* */
+  int32_t nominated_node;                 /* pod.Status.NominatedNodeName as a node index; -1 = "" */
+  int32_t row;                            /* the pod's row in `rows`; -1 = a PreFilter (the quota gate) rejected it:
+                                             [upstream] gives every node that Unschedulable status, all are potential */
+  int32_t pad0;
+} gs_preemptor;
+
+enum gs_preempt_status {
+  GS_PREEMPT_NOMINATED = 0,               /* node + victims hold the candidate pickOneNodeForPreemption chooses */
+  GS_PREEMPT_NOT_ELIGIBLE = 1,            /* PodEligibleToPreemptOthers said no */
+  GS_PREEMPT_NO_POTENTIAL_NODES = 2,      /* every node is UnschedulableAndUnresolvable */
+  GS_PREEMPT_NO_CANDIDATES = 3,           /* no node yields a victim set */
+  GS_PREEMPT_ERROR = 4                    /* no candidate and at least one node ended with an Error status */
+};
+typedef struct gs_preempt_result {
+  int32_t status;                         /* gs_preempt_status */
+  int32_t node;                           /* the nominated node, else -1 */
+  uint32_t num_victims;
+  uint32_t num_potential;                 /* nodesWherePreemptionMightHelp */
+  uint32_t num_candidates;
+  uint32_t num_errors;                    /* nodes whose SelectVictimsOnNode ended with an Error status */
+  uint64_t victims[GS_MAX_NODE_PODS];     /* uids, in victim order (the node's MoreImportantPod order) */
+} gs_preempt_result;
+
+/* node_status values */
+#define GS_PNODE_NOT_POTENTIAL 0          /* UnschedulableAndUnresolvable in the pod's row (or the pod is not eligible) */
+#define GS_PNODE_CANDIDATE 1
+#define GS_PNODE_NO_VICTIMS 2             /* "No victims found on node" (preempt.go:150-153) */
+#define GS_PNODE_UNFIT 3                  /* does not fit with every potential victim gone (preempt.go:161-163) */
+#define GS_PNODE_FITS 4                   /* every potential victim reprieved: [upstream] "expected at least one victim" */
+#define GS_PNODE_ERROR 5                  /* the second nodeInfo.RemovePod of one pod failed (preempt.go:192-194) */
+typedef struct gs_preempt_detail {        /* optional, caller-owned arrays, for n preemptors */
+  uint8_t* node_status;                   /* [n][num_nodes] GS_PNODE_* */
+  uint64_t* victim_bits;                  /* [n][num_nodes][2]: bit i = the i-th pod of the order gs_node_pods_get
+                                             returns is a victim (zero unless the node is a candidate) */
+} gs_preempt_detail;
+
+/* The dry run for n <= 128 pods that found no node, each independently, on the engine's CURRENT state (a caller that
+ * wants the state of a pod's own turn makes that pod the last of its gs_schedule_diag_nodes call). rows:
+ * [num_rows][num_nodes] status words, exactly gs_status_map.words. Per preemptor: eligibility; the potential nodes
+ * (status not UnschedulableAndUnresolvable, as gs_status_framework_code says); per potential node the potential
+ * victims (canPreempt: preemptible, lower priority, same quota) are removed from NodeInfo and, when tracked, from
+ * `used` (floored at 0, quotav1.SubtractWithNonNegativeResult); the Filters run (NodeResourcesFit, LoadAware,
+ * NodeNUMAResource; NodeNUMAResource has no PreFilterExtensions, nodenumaresource/plugin.go:271: only
+ * nodeInfo.Requested moves, which filterAmplifiedCPUs reads, plugin.go:340-373); the victims are reprieved in
+ * MoreImportantPod order while the pod still fits; after each reprieve attempt the pod is (also) a victim when
+ * used + quota_request exceeds used_limit on a key of both, and a pod removed twice makes the node an Error
+ * (preempt.go:175-200). The pick is gs_preempt_pick_node's.
+ * Waits for outstanding submissions first; modifies nothing. GS_EUNSUPPORTED, before any work, on a context with a
+ * comm initialised (several ranks) or with gs_ext_configure done; node sampling does not matter. GS_EINVAL for
+ * n > 128, a row index outside num_rows, a nominated node outside the table. Out of scope: PDBs (every victim is
+ * non-violating), nominated pods in RunFilterPluginsWithNominatedPods, extenders, prepareCandidate, the FitError text
+ * of a failed preemption, DeviceShare / Reservation AddPod / RemovePod. */
+int gs_preempt_dry_run(gs_ctx* ctx, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
+                       gs_preempt_result* out, gs_preempt_detail* detail);
+
+typedef struct gs_preempt_candidate {
+  int32_t node;
+  int32_t first_priority;                 /* priority of the first victim (the highest among the victims) */
+  int64_t sum_priorities;                 /* sum over the victims of int64(priority) + 2^31 */
+  uint32_t num_victims;
+  uint32_t pad0;
+  int64_t earliest_start_ns;              /* GetEarliestPodStartTime: earliest start among the top-priority victims */
+} gs_preempt_candidate;
+/* [upstream] pickOneNodeForPreemption with no PDB violations: lowest first_priority, then smallest sum_priorities,
+ * then fewest victims, then the LATEST earliest_start_ns, then (the reference iterates a Go map) the lowest node
+ * index. Returns the index into c of the pick, -1 for n == 0. A host function: no context, no GPU. */
+int gs_preempt_pick_node(const gs_preempt_candidate* c, uint32_t n);
+
 /* Recovery after a failed call (any return < 0 from gs_schedule / gs_evaluate / an upsert): the host state is the
  * truth — placements of the failed gs_schedule call past the last completed batch were not assumed (gs_stats.pods
  * counts the pods that were) — and the HBM mirror may hold a partial batch. gs_reset drains the device queues and
@@ -986,7 +1099,9 @@ int gs_gang_pass_carried(gs_gang_pass* p, uint64_t* uids, int8_t* states, uint32
 
 /* sizeof() of the ABI structs as compiled into the library, in this order: gs_pod, gs_node,
  * gs_node_metric, gs_pod_metric, gs_config, gs_placement, gs_stats, gs_loadaware_args, gs_cpu_topology,
- * gs_node_numa, gs_pod_allocation, gs_numa_args, gs_quota_group, gs_quota_status. */
+ * gs_node_numa, gs_pod_allocation, gs_numa_args, gs_quota_group, gs_quota_status, gs_node_devices, gs_reservation,
+ * gs_pod_ext, gs_ext_args, gs_ext_placement, gs_status_map, gs_resident_pod, gs_preemptor, gs_preempt_result,
+ * gs_preempt_detail, gs_preempt_candidate. */
 void gs_abi_sizes(uint64_t* out, uint32_t n);
 
 #ifdef __cplusplus

@@ -265,6 +265,49 @@ class GsQuotaStatus(C.Structure):
                 ("used", i64 * GS_QUOTA_DIMS)]
 
 
+# ---- ElasticQuota PostFilter: the resident-pod table and the preemption dry run ----
+GS_MAX_NODE_PODS = 128
+GS_RESIDENT_NON_PREEMPTIBLE, GS_RESIDENT_QUOTA_TRACKED, GS_RESIDENT_TERMINATING = 0x1, 0x2, 0x4
+GS_PREEMPT_NEVER = 0x1
+(GS_PREEMPT_NOMINATED, GS_PREEMPT_NOT_ELIGIBLE, GS_PREEMPT_NO_POTENTIAL_NODES, GS_PREEMPT_NO_CANDIDATES,
+ GS_PREEMPT_ERROR) = range(5)
+(GS_PNODE_NOT_POTENTIAL, GS_PNODE_CANDIDATE, GS_PNODE_NO_VICTIMS, GS_PNODE_UNFIT, GS_PNODE_FITS,
+ GS_PNODE_ERROR) = range(6)
+
+
+class GsResidentPod(C.Structure):
+    _fields_ = [("uid", u64), ("start_time_ns", i64), ("requests", i64 * GS_NUM_RES),
+                ("quota_request", i64 * GS_QUOTA_DIMS), ("quota_request_mask", u32), ("priority", i32),
+                ("quota", i32), ("flags", u32)]
+
+
+class GsPreemptor(C.Structure):
+    _fields_ = [("pod", GsPod), ("priority", i32), ("quota", i32), ("quota_request", i64 * GS_QUOTA_DIMS),
+                ("quota_request_mask", u32), ("limit_mask", u32), ("used", i64 * GS_QUOTA_DIMS),
+                ("used_limit", i64 * GS_QUOTA_DIMS), ("flags", u32), ("nominated_node", i32), ("row", i32),
+                ("pad0", i32)]
+
+
+class GsPreemptResult(C.Structure):
+    _fields_ = [("status", i32), ("node", i32), ("num_victims", u32), ("num_potential", u32),
+                ("num_candidates", u32), ("num_errors", u32), ("victims", u64 * GS_MAX_NODE_PODS)]
+
+
+class GsPreemptDetail(C.Structure):
+    _fields_ = [("node_status", C.c_void_p), ("victim_bits", C.c_void_p)]
+
+
+class GsPreemptCandidate(C.Structure):
+    _fields_ = [("node", i32), ("first_priority", i32), ("sum_priorities", i64), ("num_victims", u32), ("pad0", u32),
+                ("earliest_start_ns", i64)]
+
+
+def preempt_pick_node(cands) -> int:
+    """gs_preempt_pick_node over PREEMPT_CANDIDATE_DTYPE records: the index of the pick, -1 for none."""
+    cands = np.ascontiguousarray(cands, dtype=PREEMPT_CANDIDATE_DTYPE)
+    return load().gs_preempt_pick_node(ptr(cands), len(cands))
+
+
 # ---- Reservation + DeviceShare (SURVEY 8(f) rank 2) ----
 GS_NUM_GPU_RES = 3
 GS_GPU_CORE, GS_GPU_MEMORY_RATIO, GS_GPU_MEMORY = 0, 1, 2
@@ -358,6 +401,10 @@ NODE_DEVICES_DTYPE = np.dtype(GsNodeDevices)
 RESERVATION_DTYPE = np.dtype(GsReservation)
 POD_EXT_DTYPE = np.dtype(GsPodExt)
 EXT_PLACEMENT_DTYPE = np.dtype(GsExtPlacement)
+RESIDENT_POD_DTYPE = np.dtype(GsResidentPod)
+PREEMPTOR_DTYPE = np.dtype(GsPreemptor)
+PREEMPT_RESULT_DTYPE = np.dtype(GsPreemptResult)
+PREEMPT_CANDIDATE_DTYPE = np.dtype(GsPreemptCandidate)
 
 STRUCT_SIZES = {
     "gs_pod": C.sizeof(GsPod), "gs_node": C.sizeof(GsNode), "gs_node_metric": C.sizeof(GsNodeMetric),
@@ -369,6 +416,9 @@ STRUCT_SIZES = {
     "gs_quota_status": C.sizeof(GsQuotaStatus), "gs_node_devices": C.sizeof(GsNodeDevices),
     "gs_reservation": C.sizeof(GsReservation), "gs_pod_ext": C.sizeof(GsPodExt), "gs_ext_args": C.sizeof(GsExtArgs),
     "gs_ext_placement": C.sizeof(GsExtPlacement), "gs_status_map": C.sizeof(GsStatusMap),
+    "gs_resident_pod": C.sizeof(GsResidentPod), "gs_preemptor": C.sizeof(GsPreemptor),
+    "gs_preempt_result": C.sizeof(GsPreemptResult), "gs_preempt_detail": C.sizeof(GsPreemptDetail),
+    "gs_preempt_candidate": C.sizeof(GsPreemptCandidate),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -475,6 +525,11 @@ SIGNATURES = {
     "gs_reservations_remove": (C.c_int, [P, P, u32]),
     "gs_reservation_get": (C.c_int, [P, u64, C.POINTER(GsReservation)]),
     "gs_schedule_ext": (C.c_int, [P, P, P, u32, P, P, P]),
+    "gs_node_pods_add": (C.c_int, [P, P, P, u32]),
+    "gs_node_pods_remove": (C.c_int, [P, P, P, u32]),
+    "gs_node_pods_get": (C.c_int, [P, u32, P, u32]),
+    "gs_preempt_dry_run": (C.c_int, [P, P, u32, P, u32, P, C.POINTER(GsPreemptDetail)]),
+    "gs_preempt_pick_node": (C.c_int, [P, u32]),
 }
 
 

@@ -32,6 +32,7 @@
 #include "gs_kernels.h"
 #include "gs_numa_host.h"
 #include "gs_owned.h"
+#include "gs_preempt.h"
 #include "gs_reasons.h"
 
 using namespace gs;
@@ -121,6 +122,23 @@ struct Slot {
   bool rows_in_flight = false;      // ev_rows is recorded and no later pass has waited for it yet
   DevBuf<uint16_t> d_lwords;        // [pod of the landed pass][landed node]: the landed pass's words
   PinnedBuf<uint16_t> h_lwords;
+};
+
+// The ElasticQuota PostFilter dry run (gs_preempt_dry_run): the resident-pod table with its device image and the dry
+// run's buffers. Created by the context's first gs_node_pods_* or dry-run call: a context that makes neither holds none.
+struct PreemptState {
+  explicit PreemptState(uint32_t n) : table(n) {}
+  PreemptTable table;
+  bool rebuild = false;             // gs_reset: the next dry run uploads the whole image
+  std::vector<uint32_t> numa_idx;   // the nodes with a NUMA topology policy, as d_numa_idx holds them
+  DevBuf<uint32_t> d_numa_idx;
+  DevBuf<PrePod> d_pods;            // MAX_BATCH preemptors
+  DevBuf<PrePart> d_result;
+  DevBuf<uint16_t> d_rows;          // the status rows the call's preemptors name
+  DevBuf<uint8_t> d_status;
+  DevBuf<uint64_t> d_bits;
+  DevBuf<PrePart> d_parts;
+  size_t rows_cap = 0, out_cap = 0, parts_cap = 0;   // rows of d_rows, preemptors of d_status / d_bits, parts
 };
 
 }  // namespace
@@ -340,6 +358,8 @@ struct gs_ctx {
   std::vector<ExtRes> xres;
   std::vector<uint64_t> xres_uid;
   uint32_t xrec_cap = 0, xres_cap = 0;
+  bool ext_configured = false;       // gs_ext_configure was called (gs_preempt_dry_run refuses such a context)
+  std::unique_ptr<PreemptState> pre; // gs_node_pods_* / gs_preempt_dry_run (none until the first such call)
 };
 
 int quiesce(gs_ctx* c);   // the async submissions' worker is idle (gs_schedule_submit)
@@ -2270,7 +2290,8 @@ void gs_abi_sizes(uint64_t* out, uint32_t n) {
                         sizeof(gs_cpu_topology), sizeof(gs_node_numa), sizeof(gs_pod_allocation), sizeof(gs_numa_args),
                         sizeof(gs_quota_group), sizeof(gs_quota_status), sizeof(gs_node_devices),
                         sizeof(gs_reservation), sizeof(gs_pod_ext), sizeof(gs_ext_args), sizeof(gs_ext_placement),
-                        sizeof(gs_status_map)};
+                        sizeof(gs_status_map), sizeof(gs_resident_pod), sizeof(gs_preemptor),
+                        sizeof(gs_preempt_result), sizeof(gs_preempt_detail), sizeof(gs_preempt_candidate)};
   for (uint32_t i = 0; i < n && i < sizeof(s) / sizeof(s[0]); ++i) out[i] = s[i];
 }
 
@@ -3428,6 +3449,247 @@ int gs_preemption_candidates(const uint16_t* row, uint32_t num_nodes, uint32_t* 
   return (int)n;
 }
 
+// ---- the resident-pod table and the ElasticQuota PostFilter dry run (gs_preempt.hip, gs_preempt.cpp) ----
+namespace {
+PreemptState* preempt_state(gs_ctx* c) {
+  if (!c->pre) c->pre = std::make_unique<PreemptState>(c->N);
+  return c->pre.get();
+}
+
+// pre_potential (the kernel's potential-node test) against gs_status_framework_code, over every status word, once
+bool potential_test_agrees() {
+  static const bool ok = [] {
+    for (uint32_t w = 0; w < 0x10000u; ++w)
+      if (pre_potential(w) != (gs_status_framework_code((uint16_t)w) != 2)) return false;
+    return true;
+  }();
+  return ok;
+}
+}  // namespace
+
+int gs_node_pods_add(gs_ctx* c, const uint32_t* node_idx, const gs_resident_pod* pods, uint32_t n) {
+  if (!c || (n && (!node_idx || !pods))) return GS_EINVAL;
+  quiesce(c);
+  PreemptState* ps = preempt_state(c);
+  // the whole call is checked first: pods the call itself adds count towards the node's limit and its uids
+  std::unordered_map<uint32_t, std::vector<uint64_t>> added;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (node_idx[i] >= c->N) return fail(c, GS_EINVAL, "resident pod %u: node %u out of range", i, node_idx[i]);
+    const char* why = "";
+    if (int rc = ps->table.check_add(node_idx[i], pods[i], &why)) return fail(c, rc, "resident pod %u: %s", i, why);
+    std::vector<uint64_t>& a = added[node_idx[i]];
+    if (std::find(a.begin(), a.end(), pods[i].uid) != a.end())
+      return fail(c, GS_EINVAL, "resident pod %u: the node already holds a resident pod with this uid", i);
+    if (ps->table.count(node_idx[i]) + a.size() >= GS_MAX_NODE_PODS)
+      return fail(c, GS_EUNSUPPORTED, "resident pod %u: a node holds at most GS_MAX_NODE_PODS resident pods", i);
+    a.push_back(pods[i].uid);
+  }
+  for (uint32_t i = 0; i < n; ++i) ps->table.add(node_idx[i], pods[i]);
+  return GS_OK;
+}
+
+int gs_node_pods_remove(gs_ctx* c, const uint32_t* node_idx, const uint64_t* uids, uint32_t n) {
+  if (!c || (n && (!node_idx || !uids))) return GS_EINVAL;
+  quiesce(c);
+  PreemptState* ps = preempt_state(c);
+  for (uint32_t i = 0; i < n; ++i)
+    if (node_idx[i] >= c->N) return fail(c, GS_EINVAL, "resident pod %u: node %u out of range", i, node_idx[i]);
+  for (uint32_t i = 0; i < n; ++i) ps->table.remove(node_idx[i], uids[i]);
+  return GS_OK;
+}
+
+int gs_node_pods_get(gs_ctx* c, uint32_t node, gs_resident_pod* out, uint32_t cap) {
+  if (!c || node >= c->N || (cap && !out)) return GS_EINVAL;
+  quiesce(c);
+  if (!c->pre) return 0;
+  const uint32_t cnt = c->pre->table.count(node);
+  const PreRec* r = c->pre->table.records(node);
+  for (uint32_t j = 0; j < cnt && j < cap; ++j) {
+    gs_resident_pod& o = out[j];
+    std::memset(&o, 0, sizeof(o));
+    o.uid = r[j].uid;
+    o.start_time_ns = r[j].start;
+    for (int s = 0; s < 7; ++s) o.requests[s] = r[j].req[s];
+    for (int d = 0; d < GS_QUOTA_DIMS; ++d) o.quota_request[d] = r[j].qreq[d];
+    o.quota_request_mask = r[j].qmask;
+    o.priority = r[j].priority;
+    o.quota = r[j].quota;
+    o.flags = r[j].flags;
+  }
+  return (int)cnt;
+}
+
+int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
+                       gs_preempt_result* out, gs_preempt_detail* detail) {
+  if (!c || (n && (!p || !out))) return GS_EINVAL;
+  quiesce(c);
+  // refusals, before any work: the dry run reads one rank's whole mirror, and the extension plugins' AddPod /
+  // RemovePod (DeviceShare, Reservation) are not restated
+  if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "preemption dry run: several ranks are not supported");
+  if (c->ext_configured) return fail(c, GS_EUNSUPPORTED, "preemption dry run: a context with gs_ext_configure is not supported");
+  if (n > (uint32_t)MAX_BATCH) return fail(c, GS_EINVAL, "preemption dry run: at most %d preemptors per call", MAX_BATCH);
+  if (detail && n && (!detail->node_status || !detail->victim_bits))
+    return fail(c, GS_EINVAL, "preemption dry run: a detail without its arrays");
+  if (!n) return GS_OK;
+  int rc = ready(c);
+  if (rc) return rc;
+  const uint32_t N = c->N;
+  for (uint32_t k = 0; k < n; ++k) {
+    if ((rc = validate_pod(c, p[k].pod))) return rc;
+    if (p[k].row >= 0 && (!rows || (uint32_t)p[k].row >= num_rows))
+      return fail(c, GS_EINVAL, "preemptor %u: row %d outside the %u status rows", k, p[k].row, num_rows);
+    if (p[k].row < -1 || p[k].nominated_node < -1 || (p[k].nominated_node >= 0 && (uint32_t)p[k].nominated_node >= N))
+      return fail(c, GS_EINVAL, "preemptor %u: row or nominated node out of range", k);
+    for (int d = 0; d < GS_QUOTA_DIMS; ++d)
+      if (std::llabs(p[k].used[d]) >= kMaxExact || std::llabs(p[k].used_limit[d]) >= kMaxExact ||
+          std::llabs(p[k].quota_request[d]) >= kMaxExact)
+        return fail(c, GS_EUNSUPPORTED, "preemptor %u: a quota quantity beyond 2^53", k);
+  }
+  if (!potential_test_agrees()) return fail(c, GS_ESTATE, "preemption dry run: the potential-node test disagrees with gs_status_framework_code");
+  PreemptState* ps = preempt_state(c);
+  const PreemptTable& tb = ps->table;
+  if ((rc = flush_rows(c))) return rc;
+  if ((rc = node_prep(c))) return rc;
+  const hipStream_t st = c->st.get();
+  // nothing of an earlier run or dry run is in flight when the image and the buffers change
+  for (const Stream* s : {&c->st_ev, &c->st_rb})
+    if (*s) HIP_TRY(c, host_wait_stream(s->get()));
+  HIP_TRY(c, host_wait_stream(st));
+
+  // step 1, PodEligibleToPreemptOthers (preempt.go:61-94), and the preemptors' device vectors; the status rows the
+  // call names, compacted
+  std::vector<PrePod> hp(n);
+  std::vector<int32_t> row_map(num_rows, -1);
+  std::vector<uint32_t> used_rows;
+  for (uint32_t k = 0; k < n; ++k) {
+    const gs_preemptor& q = p[k];
+    PrePod& d = hp[k];
+    std::memset(&d, 0, sizeof(d));
+    d.v = prep_pod(c, q.pod);
+    d.skip = q.quota < 0;
+    d.check = d.skip ? 0u : (q.quota_request_mask & q.limit_mask & 0xFFu);
+    for (int j = 0; j < GS_QUOTA_DIMS; ++j) {
+      d.qreq[j] = (d.check >> j & 1u) ? q.quota_request[j] : 0;
+      d.used[j] = q.used[j];
+      d.limit[j] = q.used_limit[j];
+    }
+    d.priority = q.priority;
+    d.quota = q.quota;
+    bool eligible = !(q.flags & GS_PREEMPT_NEVER);
+    if (eligible && q.nominated_node >= 0) {
+      const uint32_t nom = (uint32_t)q.nominated_node;
+      const bool unresolvable = q.row >= 0 && !pre_potential(rows[(size_t)q.row * N + nom]);
+      if (!unresolvable) {
+        const PreRec* r = tb.records(nom);
+        for (uint32_t j = 0; j < tb.count(nom); ++j)
+          if ((r[j].flags & GS_RESIDENT_TERMINATING) && r[j].quota == q.quota && r[j].priority < q.priority) eligible = false;
+      }
+    }
+    d.active = eligible;
+    d.row = -1;
+    if (q.row >= 0) {
+      if (row_map[q.row] < 0) {
+        row_map[q.row] = (int32_t)used_rows.size();
+        used_rows.push_back((uint32_t)q.row);
+      }
+      d.row = row_map[q.row];
+    }
+  }
+
+  // the image, the policy-node list and the buffers
+  HIP_TRY(c, ps->table.sync(st, ps->rebuild));
+  ps->rebuild = false;
+  if (c->numa_on) {
+    std::vector<uint32_t> idx;
+    for (uint32_t i = 0; i < N; ++i)
+      if (c->numa[i].cfg.numa_topology_policy != GS_NUMA_POLICY_NONE) idx.push_back(i);
+    if (idx != ps->numa_idx || (!idx.empty() && !ps->d_numa_idx)) {
+      if (!idx.empty()) {
+        HIP_TRY(c, ps->d_numa_idx.alloc(4 * idx.size()));
+        HIP_TRY(c, hipMemcpy(ps->d_numa_idx.get(), idx.data(), 4 * idx.size(), hipMemcpyHostToDevice));
+      }
+      ps->numa_idx.swap(idx);
+    }
+  } else {
+    ps->numa_idx.clear();
+  }
+  const uint32_t numa_n = (uint32_t)ps->numa_idx.size();
+  const uint32_t nparts = preempt_parts(c->pf, N, numa_n);
+  if (!ps->d_pods) {
+    HIP_TRY(c, ps->d_pods.alloc(sizeof(PrePod) * MAX_BATCH));
+    HIP_TRY(c, ps->d_result.alloc(sizeof(PrePart) * MAX_BATCH));
+  }
+  if (used_rows.size() > ps->rows_cap) {
+    HIP_TRY(c, ps->d_rows.alloc(used_rows.size() * (size_t)N * 2));
+    ps->rows_cap = used_rows.size();
+  }
+  if (n > ps->out_cap) {
+    HIP_TRY(c, ps->d_status.alloc((size_t)n * N));
+    HIP_TRY(c, ps->d_bits.alloc((size_t)n * N * 16));
+    ps->out_cap = n;
+  }
+  if ((size_t)n * nparts > ps->parts_cap) {
+    HIP_TRY(c, ps->d_parts.alloc((size_t)n * nparts * sizeof(PrePart)));
+    ps->parts_cap = (size_t)n * nparts;
+  }
+  HIP_TRY(c, hipMemcpyAsync(ps->d_pods.get(), hp.data(), sizeof(PrePod) * n, hipMemcpyHostToDevice, st));
+  for (size_t r = 0; r < used_rows.size(); ++r)
+    HIP_TRY(c, hipMemcpyAsync(ps->d_rows.get() + r * N, rows + (size_t)used_rows[r] * N, (size_t)N * 2, hipMemcpyHostToDevice, st));
+
+  PreemptArgs a{};
+  a.m = c->mv;
+  a.pf = c->pf;
+  a.N = N;
+  a.npre = (int)n;
+  a.pods = ps->d_pods.get();
+  a.rows = ps->d_rows.get();
+  a.recs = tb.d_recs();
+  a.segs = tb.d_segs();
+  a.numa_idx = ps->d_numa_idx.get();
+  a.numa_n = numa_n;
+  a.status = ps->d_status.get();
+  a.bits = ps->d_bits.get();
+  a.parts = ps->d_parts.get();
+  a.nparts = nparts;
+  a.result = ps->d_result.get();
+  HIP_TRY(c, launch_preempt(a, st));
+  std::vector<PrePart> res(n);
+  HIP_TRY(c, hipMemcpyAsync(res.data(), ps->d_result.get(), sizeof(PrePart) * n, hipMemcpyDeviceToHost, st));
+  if (detail) {
+    HIP_TRY(c, hipMemcpyAsync(detail->node_status, ps->d_status.get(), (size_t)n * N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(detail->victim_bits, ps->d_bits.get(), (size_t)n * N * 16, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(c, host_wait_stream(st));
+
+  // the results; the chosen node's victim bits expanded into uids from the host table
+  for (uint32_t k = 0; k < n; ++k) {
+    gs_preempt_result& o = out[k];
+    std::memset(&o, 0, sizeof(o));
+    o.node = -1;
+    const PrePart& r = res[k];
+    if (!hp[k].active) {
+      o.status = GS_PREEMPT_NOT_ELIGIBLE;
+      continue;
+    }
+    o.num_potential = r.npot;
+    o.num_candidates = r.ncand;
+    o.num_errors = r.nerr;
+    if (!r.npot) o.status = GS_PREEMPT_NO_POTENTIAL_NODES;
+    else if (r.key.valid) {
+      o.status = GS_PREEMPT_NOMINATED;
+      o.node = r.key.node;
+      const PreRec* recs = tb.records((uint32_t)r.key.node);
+      const uint32_t cnt = tb.count((uint32_t)r.key.node);
+      for (uint32_t j = 0; j < cnt && j < GS_MAX_NODE_PODS; ++j)
+        if (r.bits[j >> 6] >> (j & 63) & 1ull) o.victims[o.num_victims++] = recs[j].uid;
+      if (o.num_victims != r.key.nvict) return fail(c, GS_ESTATE, "preemption dry run: victim bits and count disagree");
+    } else {
+      o.status = r.nerr ? GS_PREEMPT_ERROR : GS_PREEMPT_NO_CANDIDATES;
+    }
+  }
+  return GS_OK;
+}
+
 int gs_schedule_wait(gs_ctx* c, uint64_t ticket) {
   if (!c || !c->aq) return GS_EINVAL;
   AsyncQueue& q = *c->aq;
@@ -3676,6 +3938,7 @@ int gs_reset(gs_ctx* c) {
   if (!rc) rc = ext_flush_devices(c);
   if (rc) return rc;
   if ((rc = node_prep(c))) return rc;
+  if (c->pre) c->pre->rebuild = true;   // the resident-pod image: rebuilt from the host table by the next dry run
   hipError_t e = host_wait_stream(c->st.get());
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "reset: the device is unusable (%s): destroy and recreate the context",
                                    hipGetErrorString(e));
@@ -3816,6 +4079,7 @@ int gs_ext_configure(gs_ctx* c, const gs_ext_args* a) {
     return fail(c, GS_EINVAL, "extension plugin weights out of range");
   const bool rs_changed = (c->ext.enabled ^ a->enabled) & GS_EXT_RESERVATION;
   c->ext = *a;
+  c->ext_configured = true;
   if (rs_changed)   // the mirror rows carry the unmatched restore only with the Reservation plugin on
     for (uint32_t i = 0; i < c->N; ++i)
       if (c->nodes[i].valid) mark_dirty(c, i);

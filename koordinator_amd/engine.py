@@ -236,6 +236,47 @@ class Engine:
         self._chk(min(n, 0), "gs_assign_cache_get")
         return list(zip(u[:n].tolist(), t[:n].tolist()))
 
+    # ---- ElasticQuota PostFilter: the resident-pod table and the preemption dry run
+    def node_pods_add(self, node_idx, pods):
+        """gs_node_pods_add: RESIDENT_POD_DTYPE records join the resident-pod table of their nodes."""
+        node_idx = np.ascontiguousarray(node_idx, dtype=np.uint32)
+        pods = np.ascontiguousarray(pods, dtype=abi.RESIDENT_POD_DTYPE)
+        assert len(node_idx) == len(pods)
+        self._chk(lib().gs_node_pods_add(self._h, abi.ptr(node_idx), abi.ptr(pods), len(pods)), "gs_node_pods_add")
+
+    def node_pods_remove(self, node_idx, uids):
+        node_idx = np.ascontiguousarray(node_idx, dtype=np.uint32)
+        uids = np.ascontiguousarray(uids, dtype=np.uint64)
+        assert len(node_idx) == len(uids)
+        self._chk(lib().gs_node_pods_remove(self._h, abi.ptr(node_idx), abi.ptr(uids), len(uids)),
+                  "gs_node_pods_remove")
+
+    def node_pods(self, node: int):
+        """gs_node_pods_get: the node's resident pods in MoreImportantPod order (the order of the victim bits)."""
+        out = np.zeros(abi.GS_MAX_NODE_PODS, abi.RESIDENT_POD_DTYPE)
+        n = lib().gs_node_pods_get(self._h, int(node), abi.ptr(out), len(out))
+        self._chk(min(n, 0), "gs_node_pods_get")
+        return out[:n]
+
+    def preempt_dry_run(self, preemptors, rows=None, detail: bool = True):
+        """gs_preempt_dry_run: (results, node_status, victim_bits) for PREEMPTOR_DTYPE records; rows: the status
+        words [num_rows][num_nodes] their `row` fields index (gs_schedule_diag_nodes' words). node_status is
+        uint8[n][num_nodes], victim_bits uint64[n][num_nodes][2] (both None without detail)."""
+        pre = np.ascontiguousarray(preemptors, dtype=abi.PREEMPTOR_DTYPE)
+        n, N = len(pre), self.cfg.num_nodes
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.uint16).reshape(-1, N)
+        out = np.zeros(n, abi.PREEMPT_RESULT_DTYPE)
+        status = bits = None
+        d = None
+        if detail:
+            status = np.zeros((n, N), np.uint8)
+            bits = np.zeros((n, N, 2), np.uint64)
+            d = C.byref(abi.GsPreemptDetail(node_status=abi.ptr(status), victim_bits=abi.ptr(bits)))
+        self._chk(lib().gs_preempt_dry_run(self._h, abi.ptr(pre), n, abi.ptr(rows), 0 if rows is None else len(rows),
+                                           abi.ptr(out), d), "gs_preempt_dry_run")
+        return out, status, bits
+
     # ---- Reservation + DeviceShare
     def ext_configure(self, args: abi.GsExtArgs):
         self._chk(lib().gs_ext_configure(self._h, C.byref(args)), "gs_ext_configure")
