@@ -906,7 +906,8 @@ typedef struct gs_preempt_detail {        /* optional, caller-owned arrays, for 
  * comm initialised (several ranks) or with gs_ext_configure done; node sampling does not matter. GS_EINVAL for
  * n > 128, a row index outside num_rows, a nominated node outside the table. Out of scope: PDBs (every victim is
  * non-violating), nominated pods in RunFilterPluginsWithNominatedPods, extenders, prepareCandidate, the FitError text
- * of a failed preemption, DeviceShare / Reservation AddPod / RemovePod. */
+ * of a failed preemption, DeviceShare / Reservation AddPod / RemovePod. gs_preempt_dry_run_pdb (below) is the same
+ * dry run with PodDisruptionBudgets; this call ignores the lists of gs_node_pods_set_pdbs. */
 int gs_preempt_dry_run(gs_ctx* ctx, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
                        gs_preempt_result* out, gs_preempt_detail* detail);
 
@@ -922,6 +923,76 @@ typedef struct gs_preempt_candidate {
  * then fewest victims, then the LATEST earliest_start_ns, then (the reference iterates a Go map) the lowest node
  * index. Returns the index into c of the pick, -1 for n == 0. A host function: no context, no GPU. */
 int gs_preempt_pick_node(const gs_preempt_candidate* c, uint32_t n);
+
+/* ---- PodDisruptionBudgets in the dry run ----
+ * [upstream] SelectVictimsOnNode splits the potential victims with filterPodsWithPDBViolation (preempt.go:222-267):
+ * every PDB starts with a private counter DisruptionsAllowed; for each potential victim in MoreImportantPod order every
+ * PDB it matches is decremented, and the pod is "violating" iff one of those counters is then < 0. The counters run
+ * over all potential victims of the node, reprieved later or not, so the split depends on the preemptor (its priority
+ * and quota choose the potential victims) and on nothing else. The violating group is reprieved first, then the
+ * non-violating one (preempt.go:166-213), numViolatingVictim counts the violating pods whose Filter failed (a violating
+ * pod that fits and becomes a victim through the quota check alone is not counted, preempt.go:201-207), the victims
+ * slice is in reprieve order and is not sorted again, and fewest violations is the first criterion of the pick.
+ * MATCHING STAYS WITH THE CALLER: namespace, label selector ("empty selector matches nothing", "a pod without labels
+ * matches nothing") and the skip of a pod already in pdb.Status.DisruptedPods. The caller hands over, per resident pod,
+ * the ids of the PDBs that would be decremented for it. */
+#define GS_MAX_PDBS 65535u                /* PDB ids are 0 .. GS_MAX_PDBS - 1 */
+#define GS_MAX_POD_PDBS 4                 /* ids per resident pod; a pod that would need a fifth: the caller raises
+                                             GS_EUNSUPPORTED itself (the call cannot express it) */
+#define GS_PDB_NONE 0xFFFFu               /* an unused entry of a pod's list */
+#define GS_PDB_UNLIMITED 2147483647       /* INT32_MAX: the budget of an id never set; as if no such PDB existed */
+/* PDB informer handler: disruptions_allowed[i] becomes the budget (pdb.Status.DisruptionsAllowed) of PDB ids[i]; a
+ * deleted PDB: GS_PDB_UNLIMITED. Negative budgets are legal (the reference only compares the int32). GS_EINVAL for an
+ * id >= GS_MAX_PDBS (nothing of the call is applied). */
+int gs_pdbs_upsert(gs_ctx* ctx, const uint32_t* ids, const int32_t* disruptions_allowed, uint32_t n);
+/* Replaces the PDB list of resident pod uids[i] on node node_idx[i] with pdb_ids[i][0..3] (GS_PDB_NONE entries are
+ * skipped; every other uint16_t value is an id below GS_MAX_PDBS). GS_EINVAL for a node out of range, a uid that node
+ * does not hold, or an id repeated within one pod; nothing of the call is applied. A pod added by gs_node_pods_add has
+ * an empty list; removing and re-adding a pod clears its list. */
+int gs_node_pods_set_pdbs(gs_ctx* ctx, const uint32_t* node_idx, const uint64_t* uids,
+                          const uint16_t* pdb_ids /* [n][GS_MAX_POD_PDBS] */, uint32_t n);
+/* The lists of the node's pods in the order of gs_node_pods_get, ids first and GS_PDB_NONE behind them, up to cap
+ * pods; returns the node's pod count. */
+int gs_node_pods_get_pdbs(gs_ctx* ctx, uint32_t node, uint16_t* out /* [cap][GS_MAX_POD_PDBS] */, uint32_t cap);
+
+typedef struct gs_preempt_result_pdb {
+  int32_t status;                         /* gs_preempt_status */
+  int32_t node;
+  uint32_t num_victims;
+  uint32_t num_potential;
+  uint32_t num_candidates;
+  uint32_t num_errors;
+  uint32_t num_pdb_violations;            /* numViolatingVictim of the nominated node */
+  uint32_t pad0;
+  uint64_t victims[GS_MAX_NODE_PODS];     /* uids in the reference's slice order: the violating group's victims in
+                                             MoreImportantPod order, then the non-violating group's */
+} gs_preempt_result_pdb;
+typedef struct gs_preempt_detail_pdb {    /* optional, caller-owned arrays, for n preemptors */
+  uint8_t* node_status;                   /* [n][num_nodes] GS_PNODE_* */
+  uint64_t* victim_bits;                  /* [n][num_nodes][2], as gs_preempt_detail */
+  uint64_t* violating_bits;               /* [n][num_nodes][2]: the violating group among the potential victims (zero
+                                             unless the node is a candidate) */
+  uint8_t* pdb_violations;                /* [n][num_nodes]: numViolatingVictim of a candidate, else 0 */
+} gs_preempt_detail_pdb;
+/* gs_preempt_dry_run with PodDisruptionBudgets: preemptors, rows, refusals, "waits for outstanding submissions" and
+ * "modifies nothing" as there. With no list registered, or no budget ever reached, every output equals
+ * gs_preempt_dry_run's. Still out of scope: nominated pods, extenders, prepareCandidate, selector matching. */
+int gs_preempt_dry_run_pdb(gs_ctx* ctx, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
+                           gs_preempt_result_pdb* out, gs_preempt_detail_pdb* detail);
+
+typedef struct gs_preempt_candidate_pdb {
+  int32_t node;
+  int32_t first_priority;                 /* priority of victims.Pods[0], the FIRST victim in slice order: with PDBs
+                                             not always the highest among the victims */
+  int64_t sum_priorities;
+  uint32_t num_victims;
+  uint32_t num_pdb_violations;
+  int64_t earliest_start_ns;              /* GetEarliestPodStartTime: over all victims, the earliest start among those
+                                             of the highest priority (it does not assume Pods[0] is the top) */
+} gs_preempt_candidate_pdb;
+/* [upstream] pickOneNodeForPreemption in full: fewest num_pdb_violations, then the five criteria of
+ * gs_preempt_pick_node. Returns the index into c of the pick, -1 for n == 0. A host function: no context, no GPU. */
+int gs_preempt_pick_node_pdb(const gs_preempt_candidate_pdb* c, uint32_t n);
 
 /* Recovery after a failed call (any return < 0 from gs_schedule / gs_evaluate / an upsert): the host state is the
  * truth — placements of the failed gs_schedule call past the last completed batch were not assumed (gs_stats.pods
@@ -1101,7 +1172,7 @@ int gs_gang_pass_carried(gs_gang_pass* p, uint64_t* uids, int8_t* states, uint32
  * gs_node_metric, gs_pod_metric, gs_config, gs_placement, gs_stats, gs_loadaware_args, gs_cpu_topology,
  * gs_node_numa, gs_pod_allocation, gs_numa_args, gs_quota_group, gs_quota_status, gs_node_devices, gs_reservation,
  * gs_pod_ext, gs_ext_args, gs_ext_placement, gs_status_map, gs_resident_pod, gs_preemptor, gs_preempt_result,
- * gs_preempt_detail, gs_preempt_candidate. */
+ * gs_preempt_detail, gs_preempt_candidate, gs_preempt_result_pdb, gs_preempt_detail_pdb, gs_preempt_candidate_pdb. */
 void gs_abi_sizes(uint64_t* out, uint32_t n);
 
 #ifdef __cplusplus

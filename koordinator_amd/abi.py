@@ -302,6 +302,32 @@ class GsPreemptCandidate(C.Structure):
                 ("earliest_start_ns", i64)]
 
 
+# PodDisruptionBudgets in the dry run (gs_preempt_dry_run_pdb)
+GS_MAX_PDBS, GS_MAX_POD_PDBS, GS_PDB_NONE, GS_PDB_UNLIMITED = 65535, 4, 0xFFFF, 2**31 - 1
+
+
+class GsPreemptResultPdb(C.Structure):
+    _fields_ = [("status", i32), ("node", i32), ("num_victims", u32), ("num_potential", u32),
+                ("num_candidates", u32), ("num_errors", u32), ("num_pdb_violations", u32), ("pad0", u32),
+                ("victims", u64 * GS_MAX_NODE_PODS)]
+
+
+class GsPreemptDetailPdb(C.Structure):
+    _fields_ = [("node_status", C.c_void_p), ("victim_bits", C.c_void_p), ("violating_bits", C.c_void_p),
+                ("pdb_violations", C.c_void_p)]
+
+
+class GsPreemptCandidatePdb(C.Structure):
+    _fields_ = [("node", i32), ("first_priority", i32), ("sum_priorities", i64), ("num_victims", u32),
+                ("num_pdb_violations", u32), ("earliest_start_ns", i64)]
+
+
+def preempt_pick_node_pdb(cands) -> int:
+    """gs_preempt_pick_node_pdb over PREEMPT_CANDIDATE_PDB_DTYPE records: the index of the pick, -1 for none."""
+    cands = np.ascontiguousarray(cands, dtype=PREEMPT_CANDIDATE_PDB_DTYPE)
+    return load().gs_preempt_pick_node_pdb(ptr(cands), len(cands))
+
+
 def preempt_pick_node(cands) -> int:
     """gs_preempt_pick_node over PREEMPT_CANDIDATE_DTYPE records: the index of the pick, -1 for none."""
     cands = np.ascontiguousarray(cands, dtype=PREEMPT_CANDIDATE_DTYPE)
@@ -405,6 +431,8 @@ RESIDENT_POD_DTYPE = np.dtype(GsResidentPod)
 PREEMPTOR_DTYPE = np.dtype(GsPreemptor)
 PREEMPT_RESULT_DTYPE = np.dtype(GsPreemptResult)
 PREEMPT_CANDIDATE_DTYPE = np.dtype(GsPreemptCandidate)
+PREEMPT_RESULT_PDB_DTYPE = np.dtype(GsPreemptResultPdb)
+PREEMPT_CANDIDATE_PDB_DTYPE = np.dtype(GsPreemptCandidatePdb)
 
 STRUCT_SIZES = {
     "gs_pod": C.sizeof(GsPod), "gs_node": C.sizeof(GsNode), "gs_node_metric": C.sizeof(GsNodeMetric),
@@ -419,6 +447,8 @@ STRUCT_SIZES = {
     "gs_resident_pod": C.sizeof(GsResidentPod), "gs_preemptor": C.sizeof(GsPreemptor),
     "gs_preempt_result": C.sizeof(GsPreemptResult), "gs_preempt_detail": C.sizeof(GsPreemptDetail),
     "gs_preempt_candidate": C.sizeof(GsPreemptCandidate),
+    "gs_preempt_result_pdb": C.sizeof(GsPreemptResultPdb), "gs_preempt_detail_pdb": C.sizeof(GsPreemptDetailPdb),
+    "gs_preempt_candidate_pdb": C.sizeof(GsPreemptCandidatePdb),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -530,6 +560,11 @@ SIGNATURES = {
     "gs_node_pods_get": (C.c_int, [P, u32, P, u32]),
     "gs_preempt_dry_run": (C.c_int, [P, P, u32, P, u32, P, C.POINTER(GsPreemptDetail)]),
     "gs_preempt_pick_node": (C.c_int, [P, u32]),
+    "gs_pdbs_upsert": (C.c_int, [P, P, P, u32]),
+    "gs_node_pods_set_pdbs": (C.c_int, [P, P, P, P, u32]),
+    "gs_node_pods_get_pdbs": (C.c_int, [P, u32, P, u32]),
+    "gs_preempt_dry_run_pdb": (C.c_int, [P, P, u32, P, u32, P, C.POINTER(GsPreemptDetailPdb)]),
+    "gs_preempt_pick_node_pdb": (C.c_int, [P, u32]),
 }
 
 

@@ -139,6 +139,17 @@ struct PreemptState {
   DevBuf<uint64_t> d_bits;
   DevBuf<PrePart> d_parts;
   size_t rows_cap = 0, out_cap = 0, parts_cap = 0;   // rows of d_rows, preemptors of d_status / d_bits, parts
+  // PodDisruptionBudgets (gs_preempt_dry_run_pdb): none until the first gs_pdbs_upsert, gs_node_pods_set_pdbs or
+  // gs_preempt_dry_run_pdb
+  struct Pdb {
+    PdbTable table;
+    bool rebuild = false;           // gs_reset: the next dry run uploads the whole budget table
+    DevBuf<uint64_t> d_viol;        // [preemptors][N][2]
+    DevBuf<uint8_t> d_nviol;        // [preemptors][N]
+    DevBuf<PrePartPdb> d_parts, d_result;
+    size_t out_cap = 0, parts_cap = 0;
+  };
+  std::unique_ptr<Pdb> pdb;
 };
 
 }  // namespace
@@ -2291,7 +2302,8 @@ void gs_abi_sizes(uint64_t* out, uint32_t n) {
                         sizeof(gs_quota_group), sizeof(gs_quota_status), sizeof(gs_node_devices),
                         sizeof(gs_reservation), sizeof(gs_pod_ext), sizeof(gs_ext_args), sizeof(gs_ext_placement),
                         sizeof(gs_status_map), sizeof(gs_resident_pod), sizeof(gs_preemptor),
-                        sizeof(gs_preempt_result), sizeof(gs_preempt_detail), sizeof(gs_preempt_candidate)};
+                        sizeof(gs_preempt_result), sizeof(gs_preempt_detail), sizeof(gs_preempt_candidate),
+                        sizeof(gs_preempt_result_pdb), sizeof(gs_preempt_detail_pdb), sizeof(gs_preempt_candidate_pdb)};
   for (uint32_t i = 0; i < n && i < sizeof(s) / sizeof(s[0]); ++i) out[i] = s[i];
 }
 
@@ -3456,6 +3468,12 @@ PreemptState* preempt_state(gs_ctx* c) {
   return c->pre.get();
 }
 
+PreemptState::Pdb* pdb_state(gs_ctx* c) {
+  PreemptState* ps = preempt_state(c);
+  if (!ps->pdb) ps->pdb = std::make_unique<PreemptState::Pdb>();
+  return ps->pdb.get();
+}
+
 // pre_potential (the kernel's potential-node test) against gs_status_framework_code, over every status word, once
 bool potential_test_agrees() {
   static const bool ok = [] {
@@ -3519,16 +3537,99 @@ int gs_node_pods_get(gs_ctx* c, uint32_t node, gs_resident_pod* out, uint32_t ca
   return (int)cnt;
 }
 
+int gs_pdbs_upsert(gs_ctx* c, const uint32_t* ids, const int32_t* disruptions_allowed, uint32_t n) {
+  if (!c || (n && (!ids || !disruptions_allowed))) return GS_EINVAL;
+  quiesce(c);
+  for (uint32_t i = 0; i < n; ++i)
+    if (ids[i] >= GS_MAX_PDBS) return fail(c, GS_EINVAL, "PDB %u: id %u is not below GS_MAX_PDBS", i, ids[i]);
+  PreemptState::Pdb* pd = pdb_state(c);
+  for (uint32_t i = 0; i < n; ++i) pd->table.set(ids[i], disruptions_allowed[i]);
+  return GS_OK;
+}
+
+int gs_node_pods_set_pdbs(gs_ctx* c, const uint32_t* node_idx, const uint64_t* uids, const uint16_t* pdb_ids, uint32_t n) {
+  if (!c || (n && (!node_idx || !uids || !pdb_ids))) return GS_EINVAL;
+  quiesce(c);
+  // the whole call is checked first, before any state is created (a uint16_t entry is an id below GS_MAX_PDBS or
+  // GS_PDB_NONE: there is no third kind to refuse)
+  for (uint32_t i = 0; i < n; ++i) {
+    if (node_idx[i] >= c->N) return fail(c, GS_EINVAL, "PDB list %u: node %u out of range", i, node_idx[i]);
+    if (!c->pre || !c->pre->table.find(node_idx[i], uids[i]))
+      return fail(c, GS_EINVAL, "PDB list %u: the node holds no resident pod with this uid", i);
+    const uint16_t* l = pdb_ids + (size_t)i * GS_MAX_POD_PDBS;
+    for (int q = 0; q < GS_MAX_POD_PDBS; ++q)
+      for (int r = 0; r < q && l[q] != GS_PDB_NONE; ++r)
+        if (l[r] == l[q]) return fail(c, GS_EINVAL, "PDB list %u: id %u is repeated", i, (unsigned)l[q]);
+  }
+  pdb_state(c);
+  PreemptTable& tb = c->pre->table;
+  for (uint32_t i = 0; i < n; ++i) tb.set_pdbs(node_idx[i], uids[i], pdb_ids + (size_t)i * GS_MAX_POD_PDBS);
+  return GS_OK;
+}
+
+int gs_node_pods_get_pdbs(gs_ctx* c, uint32_t node, uint16_t* out, uint32_t cap) {
+  if (!c || node >= c->N || (cap && !out)) return GS_EINVAL;
+  quiesce(c);
+  if (!c->pre) return 0;
+  const uint32_t cnt = c->pre->table.count(node);
+  const PreRec* r = c->pre->table.records(node);
+  for (uint32_t j = 0; j < cnt && j < cap; ++j)
+    for (int q = 0; q < GS_MAX_POD_PDBS; ++q) out[(size_t)j * GS_MAX_POD_PDBS + q] = r[j].pdb[q];
+  return (int)cnt;
+}
+
+namespace {
+// gs_preempt_dry_run (out) and gs_preempt_dry_run_pdb (out_pdb): one of the two results, and the detail's arrays
+struct DryRunOut {
+  gs_preempt_result* out = nullptr;
+  gs_preempt_result_pdb* out_pdb = nullptr;
+  bool detail = false;
+  uint8_t* node_status = nullptr;
+  uint64_t* victim_bits = nullptr;
+  uint64_t* violating_bits = nullptr;
+  uint8_t* pdb_violations = nullptr;
+};
+int preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows, const DryRunOut& dst);
+}  // namespace
+
 int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
                        gs_preempt_result* out, gs_preempt_detail* detail) {
   if (!c || (n && (!p || !out))) return GS_EINVAL;
+  DryRunOut dst;
+  dst.out = out;
+  if (detail) {
+    dst.detail = true;
+    dst.node_status = detail->node_status;
+    dst.victim_bits = detail->victim_bits;
+  }
+  return preempt_dry_run(c, p, n, rows, num_rows, dst);
+}
+
+int gs_preempt_dry_run_pdb(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows,
+                           gs_preempt_result_pdb* out, gs_preempt_detail_pdb* detail) {
+  if (!c || (n && (!p || !out))) return GS_EINVAL;
+  DryRunOut dst;
+  dst.out_pdb = out;
+  if (detail) {
+    dst.detail = true;
+    dst.node_status = detail->node_status;
+    dst.victim_bits = detail->victim_bits;
+    dst.violating_bits = detail->violating_bits;
+    dst.pdb_violations = detail->pdb_violations;
+  }
+  return preempt_dry_run(c, p, n, rows, num_rows, dst);
+}
+
+namespace {
+int preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint16_t* rows, uint32_t num_rows, const DryRunOut& dst) {
+  const bool pdb = dst.out_pdb != nullptr;
   quiesce(c);
   // refusals, before any work: the dry run reads one rank's whole mirror, and the extension plugins' AddPod /
   // RemovePod (DeviceShare, Reservation) are not restated
   if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "preemption dry run: several ranks are not supported");
   if (c->ext_configured) return fail(c, GS_EUNSUPPORTED, "preemption dry run: a context with gs_ext_configure is not supported");
   if (n > (uint32_t)MAX_BATCH) return fail(c, GS_EINVAL, "preemption dry run: at most %d preemptors per call", MAX_BATCH);
-  if (detail && n && (!detail->node_status || !detail->victim_bits))
+  if (dst.detail && n && (!dst.node_status || !dst.victim_bits || (pdb && (!dst.violating_bits || !dst.pdb_violations))))
     return fail(c, GS_EINVAL, "preemption dry run: a detail without its arrays");
   if (!n) return GS_OK;
   int rc = ready(c);
@@ -3547,6 +3648,7 @@ int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint1
   }
   if (!potential_test_agrees()) return fail(c, GS_ESTATE, "preemption dry run: the potential-node test disagrees with gs_status_framework_code");
   PreemptState* ps = preempt_state(c);
+  PreemptState::Pdb* pd = pdb ? pdb_state(c) : nullptr;
   const PreemptTable& tb = ps->table;
   if ((rc = flush_rows(c))) return rc;
   if ((rc = node_prep(c))) return rc;
@@ -3599,6 +3701,10 @@ int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint1
   // the image, the policy-node list and the buffers
   HIP_TRY(c, ps->table.sync(st, ps->rebuild));
   ps->rebuild = false;
+  if (pdb) {
+    HIP_TRY(c, pd->table.sync(st, pd->rebuild));
+    pd->rebuild = false;
+  }
   if (c->numa_on) {
     std::vector<uint32_t> idx;
     for (uint32_t i = 0; i < N; ++i)
@@ -3628,9 +3734,21 @@ int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint1
     HIP_TRY(c, ps->d_bits.alloc((size_t)n * N * 16));
     ps->out_cap = n;
   }
-  if ((size_t)n * nparts > ps->parts_cap) {
+  if (!pdb && (size_t)n * nparts > ps->parts_cap) {
     HIP_TRY(c, ps->d_parts.alloc((size_t)n * nparts * sizeof(PrePart)));
     ps->parts_cap = (size_t)n * nparts;
+  }
+  if (pdb) {
+    if (!pd->d_result) HIP_TRY(c, pd->d_result.alloc(sizeof(PrePartPdb) * MAX_BATCH));
+    if (n > pd->out_cap) {
+      HIP_TRY(c, pd->d_viol.alloc((size_t)n * N * 16));
+      HIP_TRY(c, pd->d_nviol.alloc((size_t)n * N));
+      pd->out_cap = n;
+    }
+    if ((size_t)n * nparts > pd->parts_cap) {
+      HIP_TRY(c, pd->d_parts.alloc((size_t)n * nparts * sizeof(PrePartPdb)));
+      pd->parts_cap = (size_t)n * nparts;
+    }
   }
   HIP_TRY(c, hipMemcpyAsync(ps->d_pods.get(), hp.data(), sizeof(PrePod) * n, hipMemcpyHostToDevice, st));
   for (size_t r = 0; r < used_rows.size(); ++r)
@@ -3652,18 +3770,63 @@ int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint1
   a.parts = ps->d_parts.get();
   a.nparts = nparts;
   a.result = ps->d_result.get();
-  HIP_TRY(c, launch_preempt(a, st));
-  std::vector<PrePart> res(n);
-  HIP_TRY(c, hipMemcpyAsync(res.data(), ps->d_result.get(), sizeof(PrePart) * n, hipMemcpyDeviceToHost, st));
-  if (detail) {
-    HIP_TRY(c, hipMemcpyAsync(detail->node_status, ps->d_status.get(), (size_t)n * N, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipMemcpyAsync(detail->victim_bits, ps->d_bits.get(), (size_t)n * N * 16, hipMemcpyDeviceToHost, st));
+  std::vector<PrePart> res(pdb ? 0 : n);
+  std::vector<PrePartPdb> res_pdb(pdb ? n : 0);
+  if (pdb) {
+    a.budgets = pd->table.d_allowed();
+    a.viol = pd->d_viol.get();
+    a.nviol = pd->d_nviol.get();
+    a.parts_pdb = pd->d_parts.get();
+    a.result_pdb = pd->d_result.get();
+    HIP_TRY(c, launch_preempt_pdb(a, st));
+    HIP_TRY(c, hipMemcpyAsync(res_pdb.data(), pd->d_result.get(), sizeof(PrePartPdb) * n, hipMemcpyDeviceToHost, st));
+  } else {
+    HIP_TRY(c, launch_preempt(a, st));
+    HIP_TRY(c, hipMemcpyAsync(res.data(), ps->d_result.get(), sizeof(PrePart) * n, hipMemcpyDeviceToHost, st));
+  }
+  if (dst.detail) {
+    HIP_TRY(c, hipMemcpyAsync(dst.node_status, ps->d_status.get(), (size_t)n * N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(dst.victim_bits, ps->d_bits.get(), (size_t)n * N * 16, hipMemcpyDeviceToHost, st));
+    if (pdb) {
+      HIP_TRY(c, hipMemcpyAsync(dst.violating_bits, pd->d_viol.get(), (size_t)n * N * 16, hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipMemcpyAsync(dst.pdb_violations, pd->d_nviol.get(), (size_t)n * N, hipMemcpyDeviceToHost, st));
+    }
   }
   HIP_TRY(c, host_wait_stream(st));
 
   // the results; the chosen node's victim bits expanded into uids from the host table
-  for (uint32_t k = 0; k < n; ++k) {
-    gs_preempt_result& o = out[k];
+  for (uint32_t k = 0; pdb && k < n; ++k) {
+    gs_preempt_result_pdb& o = dst.out_pdb[k];
+    std::memset(&o, 0, sizeof(o));
+    o.node = -1;
+    const PrePartPdb& r = res_pdb[k];
+    if (!hp[k].active) {
+      o.status = GS_PREEMPT_NOT_ELIGIBLE;
+      continue;
+    }
+    o.num_potential = r.npot;
+    o.num_candidates = r.ncand;
+    o.num_errors = r.nerr;
+    if (!r.npot) o.status = GS_PREEMPT_NO_POTENTIAL_NODES;
+    else if (r.key.valid) {
+      o.status = GS_PREEMPT_NOMINATED;
+      o.node = r.key.node;
+      o.num_pdb_violations = r.key.nviol;
+      const PreRec* recs = tb.records((uint32_t)r.key.node);
+      const uint32_t cnt = tb.count((uint32_t)r.key.node);
+      // the reference's slice order: the violating group's victims, then the non-violating group's
+      for (uint64_t group : {~0ull, 0ull})
+        for (uint32_t j = 0; j < cnt && j < GS_MAX_NODE_PODS; ++j) {
+          const uint64_t bit = 1ull << (j & 63);
+          if ((r.bits[j >> 6] & bit) && (r.viol[j >> 6] & bit) == (group & bit)) o.victims[o.num_victims++] = recs[j].uid;
+        }
+      if (o.num_victims != r.key.nvict) return fail(c, GS_ESTATE, "preemption dry run: victim bits and count disagree");
+    } else {
+      o.status = r.nerr ? GS_PREEMPT_ERROR : GS_PREEMPT_NO_CANDIDATES;
+    }
+  }
+  for (uint32_t k = 0; !pdb && k < n; ++k) {
+    gs_preempt_result& o = dst.out[k];
     std::memset(&o, 0, sizeof(o));
     o.node = -1;
     const PrePart& r = res[k];
@@ -3689,6 +3852,7 @@ int gs_preempt_dry_run(gs_ctx* c, const gs_preemptor* p, uint32_t n, const uint1
   }
   return GS_OK;
 }
+}  // namespace
 
 int gs_schedule_wait(gs_ctx* c, uint64_t ticket) {
   if (!c || !c->aq) return GS_EINVAL;
@@ -3939,6 +4103,7 @@ int gs_reset(gs_ctx* c) {
   if (rc) return rc;
   if ((rc = node_prep(c))) return rc;
   if (c->pre) c->pre->rebuild = true;   // the resident-pod image: rebuilt from the host table by the next dry run
+  if (c->pre && c->pre->pdb) c->pre->pdb->rebuild = true;   // ... and the budget table
   hipError_t e = host_wait_stream(c->st.get());
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "reset: the device is unusable (%s): destroy and recreate the context",
                                    hipGetErrorString(e));

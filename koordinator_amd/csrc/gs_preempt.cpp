@@ -83,6 +83,7 @@ void PreemptTable::add(uint32_t node, const gs_resident_pod& p) {
   r.quota = p.quota;
   r.flags = p.flags;
   r.qmask = p.quota_request_mask;
+  for (int q = 0; q < GS_MAX_POD_PDBS; ++q) r.pdb[q] = GS_PDB_NONE;
   PreRec* b = &pool_[sg.off];
   PreRec* pos = std::upper_bound(b, b + sg.cnt, r, more_important);
   std::memmove(pos + 1, pos, sizeof(PreRec) * (size_t)(b + sg.cnt - pos));
@@ -101,6 +102,23 @@ void PreemptTable::remove(uint32_t node, uint64_t uid) {
     mark(node);
     return;
   }
+}
+
+const PreRec* PreemptTable::find(uint32_t node, uint64_t uid) const {
+  const PreSeg& sg = segs_[node];
+  for (uint32_t j = 0; j < sg.cnt; ++j)
+    if (pool_[sg.off + j].uid == uid) return &pool_[sg.off + j];
+  return nullptr;
+}
+
+void PreemptTable::set_pdbs(uint32_t node, uint64_t uid, const uint16_t* ids) {
+  PreRec* r = const_cast<PreRec*>(find(node, uid));
+  if (!r) return;
+  int k = 0;   // the ids first, GS_PDB_NONE behind them
+  for (int q = 0; q < GS_MAX_POD_PDBS; ++q)
+    if (ids[q] != GS_PDB_NONE) r->pdb[k++] = ids[q];
+  for (; k < GS_MAX_POD_PDBS; ++k) r->pdb[k] = GS_PDB_NONE;
+  mark(node);
 }
 
 hipError_t PreemptTable::sync(hipStream_t st, bool rebuild) {
@@ -135,7 +153,51 @@ hipError_t PreemptTable::sync(hipStream_t st, bool rebuild) {
   return hipStreamSynchronize(st);   // the copies read pool_ / segs_, which the next table call may move
 }
 
+void PdbTable::set(uint32_t id, int32_t allowed) {
+  if (allowed_[id] == allowed) return;
+  allowed_[id] = allowed;
+  if (!dirty_[id]) {
+    dirty_[id] = 1;
+    dirty_list_.push_back(id);
+  }
+}
+
+// Changed entries beyond which the whole 256-KB table goes in one copy. An estimate, not a measurement: a 4-byte copy
+// from pageable memory costs a few microseconds of launch overhead whatever its size, the whole table some tens of
+// microseconds at PCIe rates, so a few dozen entry copies already cost as much (the segments' eighth would be 8,191).
+constexpr size_t kPdbWholeAbove = 32;
+
+hipError_t PdbTable::sync(hipStream_t st, bool rebuild) {
+  hipError_t e;
+  if (!d_allowed_) {
+    if ((e = d_allowed_.alloc(sizeof(int32_t) * allowed_.size()))) return e;
+    rebuild = true;
+  }
+  if (rebuild || dirty_list_.size() > kPdbWholeAbove) {
+    if ((e = hipMemcpyAsync(d_allowed_.get(), allowed_.data(), sizeof(int32_t) * allowed_.size(), hipMemcpyHostToDevice, st)))
+      return e;
+  } else {
+    for (uint32_t id : dirty_list_)
+      if ((e = hipMemcpyAsync(d_allowed_.get() + id, &allowed_[id], sizeof(int32_t), hipMemcpyHostToDevice, st))) return e;
+  }
+  for (uint32_t id : dirty_list_) dirty_[id] = 0;
+  dirty_list_.clear();
+  return hipStreamSynchronize(st);
+}
+
 }  // namespace gs
+
+extern "C" int gs_preempt_pick_node_pdb(const gs_preempt_candidate_pdb* c, uint32_t n) {
+  if (!c || !n) return -1;
+  auto key = [&](uint32_t i) {
+    return gs::PreKeyPdb{c[i].sum_priorities, c[i].earliest_start_ns, c[i].first_priority, c[i].num_victims, c[i].node, 1,
+                         c[i].num_pdb_violations, 0u};
+  };
+  uint32_t best = 0;
+  for (uint32_t i = 1; i < n; ++i)
+    if (gs::pre_key_before(key(i), key(best))) best = i;
+  return (int)best;
+}
 
 extern "C" int gs_preempt_pick_node(const gs_preempt_candidate* c, uint32_t n) {
   if (!c || !n) return -1;

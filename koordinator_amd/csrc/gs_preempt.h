@@ -23,7 +23,7 @@ struct PreRec {
   int32_t quota;
   uint32_t flags;        // GS_RESIDENT_*
   uint32_t qmask;
-  uint64_t pad;
+  uint16_t pdb[GS_MAX_POD_PDBS];   // gs_node_pods_set_pdbs: the PDBs decremented for this pod, GS_PDB_NONE = no entry
 };
 static_assert(sizeof(PreRec) == 160, "PreRec layout");
 
@@ -66,6 +66,25 @@ struct PrePart {
 };
 static_assert(sizeof(PrePart) == 64, "PrePart layout");
 
+// The same three for gs_preempt_dry_run_pdb: the key begins with the violation count
+struct PreKeyPdb {
+  int64_t sum;
+  int64_t earliest;      // GetEarliestPodStartTime: the earliest start among the victims of the highest priority
+  int32_t first;         // the first victim in slice order (violating group first): not always the highest priority
+  uint32_t nvict;
+  int32_t node;
+  int32_t valid;
+  uint32_t nviol;        // numViolatingVictim
+  uint32_t pad;
+};
+struct PrePartPdb {
+  PreKeyPdb key;
+  uint64_t bits[2];      // the key's victim bits
+  uint64_t viol[2];      // ... and its violating group
+  uint32_t npot, ncand, nerr, pad;
+};
+static_assert(sizeof(PreKeyPdb) == 40 && sizeof(PrePartPdb) == 88, "PrePartPdb layout");
+
 // the potential-node test on a status word: framework.Code != UnschedulableAndUnresolvable, as
 // gs_status_framework_code reads the word (Fit and LoadAware statuses are Unschedulable; NodeNUMAResource's reasons
 // 1, 2, 3, 5, 6, 7, 9 are UnschedulableAndUnresolvable: gs_reasons.cpp kNuma)
@@ -96,12 +115,21 @@ struct PreemptArgs {
   PrePart* parts;            // [npre][nparts]: one per workgroup of either instantiation
   uint32_t nparts;
   PrePart* result;           // [npre]
+  // gs_preempt_dry_run_pdb only (launch_preempt_pdb; parts and result above are unused there)
+  const int32_t* budgets;    // [GS_MAX_PDBS] DisruptionsAllowed, GS_PDB_UNLIMITED where never set
+  uint64_t* viol;            // [npre][N][2]: preempt_partition_kernel writes the violating group of the potential
+                             // victims, the node kernel reads it and zeroes it unless the node is a candidate
+  uint8_t* nviol;            // [npre][N] numViolatingVictim
+  PrePartPdb* parts_pdb;     // [npre][nparts]
+  PrePartPdb* result_pdb;    // [npre]
 };
 // workgroups of the two node passes for N nodes of which numa_n carry a NUMA topology policy
 uint32_t preempt_parts(const Profile& pf, uint32_t N, uint32_t numa_n);
 // preempt_nodes_kernel over every node (policy nodes through numa_idx in a second instantiation) and the
 // one-workgroup-per-preemptor pick pass behind it
 hipError_t launch_preempt(const PreemptArgs& a, hipStream_t st);
+// the same with PodDisruptionBudgets: preempt_partition_kernel, preempt_nodes_pdb_kernel, preempt_pick_pdb_kernel
+hipError_t launch_preempt_pdb(const PreemptArgs& a, hipStream_t st);
 
 // the pick of step 4 as a strict order: a is picked before b
 #ifdef __HIPCC__
@@ -109,6 +137,20 @@ __host__ __device__
 #endif
 inline bool pre_key_before(const PreKey& a, const PreKey& b) {
   if (a.valid != b.valid) return a.valid > b.valid;
+  if (a.first != b.first) return a.first < b.first;
+  if (a.sum != b.sum) return a.sum < b.sum;
+  if (a.nvict != b.nvict) return a.nvict < b.nvict;
+  if (a.earliest != b.earliest) return a.earliest > b.earliest;
+  return a.node < b.node;
+}
+
+// pickOneNodeForPreemption in full: fewest PDB violations first, then the order above
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+inline bool pre_key_before(const PreKeyPdb& a, const PreKeyPdb& b) {
+  if (a.valid != b.valid) return a.valid > b.valid;
+  if (a.nviol != b.nviol) return a.nviol < b.nviol;
   if (a.first != b.first) return a.first < b.first;
   if (a.sum != b.sum) return a.sum < b.sum;
   if (a.nvict != b.nvict) return a.nvict < b.nvict;
@@ -128,6 +170,9 @@ class PreemptTable {
   int check_add(uint32_t node, const gs_resident_pod& p, const char** why) const;
   void add(uint32_t node, const gs_resident_pod& p);
   void remove(uint32_t node, uint64_t uid);
+  // the record of uid on node, nullptr if the node does not hold it; set_pdbs replaces its PDB list
+  const PreRec* find(uint32_t node, uint64_t uid) const;
+  void set_pdbs(uint32_t node, uint64_t uid, const uint16_t* ids);
   uint32_t count(uint32_t node) const { return segs_[node].cnt; }
   const PreRec* records(uint32_t node) const { return pool_.data() + segs_[node].off; }
   // brings the device image up to date on st (the caller has made sure no kernel reads it); rebuild: all of it
@@ -146,6 +191,23 @@ class PreemptTable {
   DevBuf<PreRec> d_pool_;
   DevBuf<PreSeg> d_segs_;
   size_t d_pool_cap_ = 0;                 // records the device pool holds
+};
+
+// ---- the PodDisruptionBudget table (gs_pdbs_upsert): DisruptionsAllowed by PDB id, and its device image ----
+class PdbTable {
+ public:
+  PdbTable() : allowed_(GS_MAX_PDBS, GS_PDB_UNLIMITED), dirty_(GS_MAX_PDBS, 0) {}
+  void set(uint32_t id, int32_t allowed);
+  int32_t get(uint32_t id) const { return allowed_[id]; }
+  // as PreemptTable::sync: the changed entries one by one, or the whole table once more than a few dozen changed
+  hipError_t sync(hipStream_t st, bool rebuild);
+  const int32_t* d_allowed() const { return d_allowed_.get(); }
+
+ private:
+  std::vector<int32_t> allowed_;
+  std::vector<uint8_t> dirty_;
+  std::vector<uint32_t> dirty_list_;
+  DevBuf<int32_t> d_allowed_;
 };
 
 }  // namespace gs

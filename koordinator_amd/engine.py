@@ -277,6 +277,54 @@ class Engine:
                                            abi.ptr(out), d), "gs_preempt_dry_run")
         return out, status, bits
 
+    # ---- PodDisruptionBudgets in the dry run
+    def pdbs_upsert(self, ids, disruptions_allowed):
+        """gs_pdbs_upsert: the budget (DisruptionsAllowed) of each PDB id; abi.GS_PDB_UNLIMITED deletes a PDB."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        allowed = np.ascontiguousarray(disruptions_allowed, dtype=np.int32)
+        assert len(ids) == len(allowed)
+        self._chk(lib().gs_pdbs_upsert(self._h, abi.ptr(ids), abi.ptr(allowed), len(ids)), "gs_pdbs_upsert")
+
+    def node_pods_set_pdbs(self, node_idx, uids, pdb_ids):
+        """gs_node_pods_set_pdbs: pdb_ids uint16[n][4] (abi.GS_PDB_NONE = no entry) replaces the PDB list of resident
+        pod uids[i] on node node_idx[i]."""
+        node_idx = np.ascontiguousarray(node_idx, dtype=np.uint32)
+        uids = np.ascontiguousarray(uids, dtype=np.uint64)
+        pdb_ids = np.ascontiguousarray(pdb_ids, dtype=np.uint16).reshape(-1, abi.GS_MAX_POD_PDBS)
+        assert len(node_idx) == len(uids) == len(pdb_ids)
+        self._chk(lib().gs_node_pods_set_pdbs(self._h, abi.ptr(node_idx), abi.ptr(uids), abi.ptr(pdb_ids), len(uids)),
+                  "gs_node_pods_set_pdbs")
+
+    def node_pods_pdbs(self, node: int):
+        """gs_node_pods_get_pdbs: uint16[count][4], the PDB lists of the node's pods in the order of node_pods."""
+        out = np.full((abi.GS_MAX_NODE_PODS, abi.GS_MAX_POD_PDBS), abi.GS_PDB_NONE, np.uint16)
+        n = lib().gs_node_pods_get_pdbs(self._h, int(node), abi.ptr(out), len(out))
+        self._chk(min(n, 0), "gs_node_pods_get_pdbs")
+        return out[:n]
+
+    def preempt_dry_run_pdb(self, preemptors, rows=None, detail: bool = True):
+        """gs_preempt_dry_run_pdb: (results, node_status, victim_bits, violating_bits, pdb_violations) for
+        PREEMPTOR_DTYPE records, as preempt_dry_run; violating_bits is uint64[n][num_nodes][2], pdb_violations
+        uint8[n][num_nodes] (the four arrays are None without detail)."""
+        pre = np.ascontiguousarray(preemptors, dtype=abi.PREEMPTOR_DTYPE)
+        n, N = len(pre), self.cfg.num_nodes
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.uint16).reshape(-1, N)
+        out = np.zeros(n, abi.PREEMPT_RESULT_PDB_DTYPE)
+        status = bits = viol = nviol = None
+        d = None
+        if detail:
+            status = np.zeros((n, N), np.uint8)
+            bits = np.zeros((n, N, 2), np.uint64)
+            viol = np.zeros((n, N, 2), np.uint64)
+            nviol = np.zeros((n, N), np.uint8)
+            d = C.byref(abi.GsPreemptDetailPdb(node_status=abi.ptr(status), victim_bits=abi.ptr(bits),
+                                               violating_bits=abi.ptr(viol), pdb_violations=abi.ptr(nviol)))
+        self._chk(lib().gs_preempt_dry_run_pdb(self._h, abi.ptr(pre), n, abi.ptr(rows),
+                                               0 if rows is None else len(rows), abi.ptr(out), d),
+                  "gs_preempt_dry_run_pdb")
+        return out, status, bits, viol, nviol
+
     # ---- Reservation + DeviceShare
     def ext_configure(self, args: abi.GsExtArgs):
         self._chk(lib().gs_ext_configure(self._h, C.byref(args)), "gs_ext_configure")

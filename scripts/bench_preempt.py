@@ -10,7 +10,12 @@ sample of the same cluster, scaled by nodes / sample: an ESTIMATE, marked as suc
 
   --only N   N preemptors per call only, no CPU estimate, for a profiler:
              rocprofv3 --kernel-trace --stats -d OUT -- python scripts/bench_preempt.py --only 16 --calls 5
-             (preempt_nodes_kernel<...> and preempt_pick_kernel are the dry run's kernels)"""
+             (preempt_nodes_kernel<...> and preempt_pick_kernel are the dry run's kernels)
+  --pdbs K   the cost of PodDisruptionBudgets instead: K PDBs with budgets 0 / 1 / 2 in turn, every resident in 0-2
+             of them; gs_preempt_dry_run_pdb and gs_preempt_dry_run on the same table, alternating in one session.
+             Prints ms per call of both (min / median / max over --calls) and the share of candidate nodes with a
+             non-empty violating group. With --only N under rocprofv3: preempt_partition_kernel,
+             preempt_nodes_pdb_kernel<...> and preempt_pick_pdb_kernel are the new call's kernels."""
 import argparse
 import json
 import os
@@ -29,6 +34,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--sample-nodes", type=int, default=500)
+    ap.add_argument("--pdbs", type=int, default=0)
     args = ap.parse_args()
 
     from koordinator_amd import abi, config, synth
@@ -63,6 +69,11 @@ def main():
     slots = int(sum(max(8, 1 << int(np.ceil(np.log2(max(int(c), 1))))) for c in counts.tolist() if c))
     out = {"what": "gs_preempt_dry_run", "nodes": N, "residents": int(len(res)), "table_add_s": round(t_add, 3),
            "table_device_bytes": slots * 160 + 8 * N, "per_call": {}}
+    if args.pdbs:
+        out = pdb_cost(eng, args, node_idx, res, preemptors, out)
+        eng.close()
+        print(json.dumps(out))
+        return
     first = True
     churn = s.permutation(N)[:64]
     for n in ([args.only] if args.only else [1, 16, 128]):
@@ -121,6 +132,48 @@ def main():
                                "s_per_preemptor_scaled": round(dt * N / S, 2),
                                "note": "Python restatement over the oracle's Filter, scaled by nodes / sample"}
     print(json.dumps(out))
+
+
+def pdb_cost(eng, args, node_idx, res, preemptors, out):
+    """gs_preempt_dry_run_pdb against gs_preempt_dry_run on the same table, alternating."""
+    from koordinator_amd import abi
+    s = np.random.RandomState(2)
+    K, M = args.pdbs, len(res)
+    ids = np.full((M, abi.GS_MAX_POD_PDBS), abi.GS_PDB_NONE, np.uint16)
+    n = s.randint(0, 3, M)
+    a, b = s.randint(0, K, M), s.randint(0, K - 1, M)
+    b = np.where(b >= a, b + 1, b)                      # distinct from a
+    ids[n >= 1, 0] = a[n >= 1]
+    ids[n >= 2, 1] = b[n >= 2]
+    t0 = time.perf_counter()
+    eng.node_pods_set_pdbs(node_idx, res["uid"], ids)
+    eng.pdbs_upsert(np.arange(K, dtype=np.uint32), (np.arange(K) % 3).astype(np.int32))
+    out.update({"what": "gs_preempt_dry_run_pdb vs gs_preempt_dry_run", "pdbs": K, "memberships_per_resident": "0-2",
+                "budgets": "0 / 1 / 2 in turn", "set_lists_and_budgets_s": round(time.perf_counter() - t0, 3)})
+
+    def stat(ts):
+        return {"min": round(1e3 * min(ts), 3), "median": round(1e3 * float(np.median(ts)), 3), "max": round(1e3 * max(ts), 3)}
+    for n in ([args.only] if args.only else [1, 16, 128]):
+        pre = preemptors(n)
+        r, status, _, viol, nviol = eng.preempt_dry_run_pdb(pre, None, detail=True)    # (the first call uploads)
+        eng.preempt_dry_run(pre, None, detail=False)
+        cand = status == abi.GS_PNODE_CANDIDATE
+        t_old, t_new = [], []
+        for i in range(args.calls):
+            for which in ((0, 1) if i % 2 == 0 else (1, 0)):
+                t0 = time.perf_counter()
+                if which:
+                    eng.preempt_dry_run_pdb(pre, None, detail=False)
+                else:
+                    eng.preempt_dry_run(pre, None, detail=False)
+                (t_new if which else t_old).append(time.perf_counter() - t0)
+        out["per_call"][str(n)] = {
+            "ms_per_call_without_pdbs": stat(t_old), "ms_per_call_with_pdbs": stat(t_new),
+            "candidates_mean": float(r["num_candidates"].mean()),
+            "share_of_candidates_with_violating_group": round(float((cand & viol.any(axis=2)).sum() / max(cand.sum(), 1)), 3),
+            "share_of_candidates_with_violations": round(float((cand & (nviol > 0)).sum() / max(cand.sum(), 1)), 3),
+            "nominated": int((r["status"] == abi.GS_PREEMPT_NOMINATED).sum())}
+    return out
 
 
 if __name__ == "__main__":
