@@ -397,10 +397,16 @@ int gs_node_metrics_upsert(gs_ctx* ctx, const uint32_t* idx, const gs_node_metri
 int gs_pods_assign(gs_ctx* ctx, const uint32_t* node_idx, const gs_pod* pods, const int64_t* timestamps_ns,
                    uint32_t n);
 int gs_pods_unassign(gs_ctx* ctx, const uint32_t* node_idx, const gs_pod* pods, uint32_t n);
-/* The scheduler cache's ForgetPod of assumed pods (gs_schedule placed them) once their Reserve is undone: a rejected
- * Permit or a failed binding cycle ([upstream] schedule_one.go: RunReservePluginsUnreserve + Cache.ForgetPod):
- * NodeInfo.RemovePod, LoadAware Unreserve (podAssignCache.unAssign, load_aware.go:265-267) and NodeNUMAResource
- * Unreserve (resourceManager.Release, nodenumaresource/plugin.go:467-476). node_idx[i]: the node pod i was assumed on. */
+/* The scheduler cache's ForgetPod of assumed pods (gs_schedule / gs_schedule_ext placed them) once their Reserve is
+ * undone: a rejected Permit or a failed binding cycle ([upstream] schedule_one.go: RunReservePluginsUnreserve +
+ * Cache.ForgetPod): NodeInfo.RemovePod, LoadAware Unreserve (podAssignCache.unAssign, load_aware.go:265-267) and
+ * NodeNUMAResource Unreserve (resourceManager.Release, nodenumaresource/plugin.go:467-476). node_idx[i]: the node pod i
+ * was assumed on. A pod gs_schedule_ext placed first gets the Unreserves of the Reserve recorded for it
+ * (gs_ext_reserved_get): DeviceShare's (deviceshare/plugin.go:432-451: the recorded amounts leave `used` of the
+ * recorded minors the Device row still has, floored at 0), Reservation's (reservation/plugin.go:572-594: the recorded
+ * amounts leave `allocated` of the reservation if it still exists, floored at 0, keys kept; assigned_pods - 1) and
+ * NodeInfo.RemovePod of its GPU-name / extended-resource requests. The whole call is validated first: GS_EINVAL for a
+ * node index out of range or a pod whose recorded node is not node_idx[i], and then nothing has changed. */
 int gs_pods_forget(gs_ctx* ctx, const uint32_t* node_idx, const gs_pod* pods, uint32_t n);
 /* podAssignCache's pod informer handlers OnAdd / OnUpdate / OnDelete (loadaware/pod_assign_cache.go:82-117):
  * node_idx[i] = pod.Spec.NodeName as a node index (-1: "", a pending pod), the GS_POD_TERMINATED flag =
@@ -664,9 +670,16 @@ int gs_reservation_get(gs_ctx* ctx, uint64_t uid, gs_reservation* out);   /* 1 =
 /* gs_schedule with the Reservation / DeviceShare plugins: ext[i] (ext may be NULL: no pod uses them) holds pod i's
  * plugin inputs; ext_out[i] (may be NULL) receives the reservation and GPU minors the Reserve assumed. Pods on the
  * extension path need no node sampling, and one rank or several over the score-row exchange (each extension pod then
- * runs whole on every rank; GS_EUNSUPPORTED under GS_XCHG=levels). */
+ * runs whole on every rank; GS_EUNSUPPORTED under GS_XCHG=levels). What an extension pod's Reserve applied (GPU minors,
+ * the reservation, GPU-name / extended-resource requests) is recorded under its uid until gs_pods_forget undoes it or
+ * gs_pods_unassign drops it. */
 int gs_schedule_ext(gs_ctx* ctx, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
                     gs_placement* out, gs_ext_placement* ext_out);
+/* The extension-path Reserve recorded for an assumed pod: what gs_pods_forget would undo, and what PreBind writes
+ * (DeviceShare's device-allocated annotation, Reservation's reservation-allocated). 1 = found: *node and the
+ * reservation_uid / gpu_minor_mask / gpu_count / gpu_per_instance of *out are filled, the rest of *out is 0;
+ * 0 = none (never placed by gs_schedule_ext, or forgotten / unassigned since). */
+int gs_ext_reserved_get(gs_ctx* ctx, uint64_t uid, uint32_t* node, gs_ext_placement* out);
 
 /* Multi-GPU: nodes are sharded in contiguous ranges [r*ceil(N/R), (r+1)*ceil(N/R)); every rank keeps the full
  * mirror (replicated deltas) and evaluates only its shard. Per batch the shards' score rows are all-gathered and every

@@ -555,6 +555,7 @@ SIGNATURES = {
     "gs_reservations_remove": (C.c_int, [P, P, u32]),
     "gs_reservation_get": (C.c_int, [P, u64, C.POINTER(GsReservation)]),
     "gs_schedule_ext": (C.c_int, [P, P, P, u32, P, P, P]),
+    "gs_ext_reserved_get": (C.c_int, [P, u64, P, P]),
     "gs_node_pods_add": (C.c_int, [P, P, P, u32]),
     "gs_node_pods_remove": (C.c_int, [P, P, P, u32]),
     "gs_node_pods_get": (C.c_int, [P, u32, P, u32]),

@@ -214,6 +214,22 @@ struct gs_local_group {
   }
 };
 
+// What the extension path's Reserve (ext_schedule_one) applied for one assumed pod: gs_pods_forget takes exactly this
+// back (DeviceShare Unreserve, Reservation Unreserve, NodeInfo.RemovePod of the scalars), gs_ext_reserved_get reports it.
+struct ExtReserved {
+  uint32_t node = 0;
+  uint32_t gpu_minor_mask = 0;                  // gs_ext_placement.gpu_minor_mask
+  int32_t gpu_count = 0;
+  uint32_t gpu_keys = 0;                        // the keys of each minor's DeviceAllocation.Resources (bit = gs_gpu_res)
+  int64_t gpu_per_instance[GS_NUM_GPU_RES] = {};
+  uint64_t reservation_uid = 0;                 // 0: assumed into none
+  uint32_t rsv_slots = 0;                       // slots of the reservation's Allocated the pod's requests were added to
+  int64_t rsv_added[GS_NUM_RES] = {};
+  uint32_t gpu_names = 0, xres = 0;             // NodeInfo.AddPod: GPU names / registered extended resources added
+  int64_t gpu_name_req[GS_NUM_GPU_NAMES] = {};
+  int64_t xres_req[GS_MAX_XRES] = {};
+};
+
 // Members are destroyed in reverse order: the buffers go first, then the events, then the streams (gs_destroy).
 struct gs_ctx {
   Stream st;
@@ -229,7 +245,7 @@ struct gs_ctx {
   // (gs_schedule). cur_slot: the slot whose batch is current; between runs its buffers serve as scratch (current_slot)
   Slot slot[2];
   int cur_slot = 0;
-  std::unordered_set<uint64_t> ext_reserved;   // pods placed with an extension-path Reserve (gs_schedule_ext)
+  std::unordered_map<uint64_t, ExtReserved> ext_reserved;   // assumed pods' extension-path Reserves (gs_schedule_ext)
   gs_config cfg{};
   std::string err;
   std::unique_ptr<AsyncQueue> aq;   // gs_schedule_submit's worker (created by the first submission)
@@ -1949,8 +1965,9 @@ bool is_ext_pod(const gs_ctx* c, const gs_pod_ext& e) {
 // (device_allocator.go:397-467; minors by device score descending, then minor), within the node's NUMA affinity
 // (aff: 0x10 | zone-slot mask, 0 = none; device_allocator.go:148-152)
 int ext_device_reserve(gs_ctx* c, uint32_t node, const int64_t preq[3], uint32_t pmask, gs_ext_placement* eo,
-                       uint32_t aff) {
+                       uint32_t aff, uint32_t* keys) {
   gs_node_devices& d = c->devs[node];
+  *keys = 0;
   if (!d.has_device) return GS_OK;
   const DevNode img = dev_image(c, node);
   int64_t total_mem = -1;
@@ -2006,6 +2023,7 @@ int ext_device_reserve(gs_ctx* c, uint32_t node, const int64_t preq[3], uint32_t
   }
   eo->gpu_count = (int32_t)count;
   for (int r = 0; r < 3; ++r) eo->gpu_per_instance[r] = (m >> r & 1u) ? inst[r] : 0;
+  *keys = m & 7u;
   dev_mark(c, node);
   return GS_OK;
 }
@@ -2238,7 +2256,9 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     if ((rc = numa_reserve(c, pod, v, pd))) return rc;
     out->flags = xo.nflags & ~PL_INTERNAL_FLAGS;
   }
-  if (gmask && (rc = ext_device_reserve(c, node, greq, gmask, eo, xo.aff))) {
+  ExtReserved done{};   // what the Reserves below apply
+  done.node = node;
+  if (gmask && (rc = ext_device_reserve(c, node, greq, gmask, eo, xo.aff, &done.gpu_keys))) {
     // the reference runs every plugin's Unreserve on a Reserve failure: NodeNUMAResource's allocation goes again
     if (c->numa_on && c->numa_uid_node.count(pod.uid)) {
       numa_release(c->numa[node], pod.uid);
@@ -2261,17 +2281,34 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
         if ((r.resource_names_mask >> s & 1u) && (pod.request_mask >> s & 1u)) {
           r.allocated[s] = ((r.allocated_mask >> s & 1u) ? r.allocated[s] : 0) + pod.requests[s];
           r.allocated_mask |= 1u << s;
+          done.rsv_slots |= 1u << s;
+          done.rsv_added[s] = pod.requests[s];
         }
       r.assigned_pods += 1;
       eo->reservation_uid = r.uid;
     }
   }
   for (int n = 0; n < GS_NUM_GPU_NAMES; ++n)   // NodeInfo.AddPod of the GPU-name scalars
-    if (gpu_names_all >> n & 1u) { c->devs[node].requested[n] += e.gpu_requests[n]; dev_mark(c, node); }
+    if (gpu_names_all >> n & 1u) {
+      c->devs[node].requested[n] += e.gpu_requests[n];
+      done.gpu_name_req[n] = e.gpu_requests[n];
+      dev_mark(c, node);
+    }
   for (int x = 0; x < GS_MAX_XRES; ++x)         // ... and of the registered extended resources
-    if (xres_all >> x & 1u) { c->devs[node].xres_requested[x] += e.xres_requests[x]; dev_mark(c, node); }
-  if (gmask || (rs_on && rec_i >= 0 && h_xnom[rec_i] >= 0) || gpu_names_all || xres_all)
-    c->ext_reserved.insert(pod.uid);   // gs_pods_forget cannot undo these Reserves
+    if (xres_all >> x & 1u) {
+      c->devs[node].xres_requested[x] += e.xres_requests[x];
+      done.xres_req[x] = e.xres_requests[x];
+      dev_mark(c, node);
+    }
+  if (gmask || (rs_on && rec_i >= 0 && h_xnom[rec_i] >= 0) || gpu_names_all || xres_all) {
+    done.gpu_minor_mask = eo->gpu_minor_mask;
+    done.gpu_count = eo->gpu_count;
+    for (int r = 0; r < GS_NUM_GPU_RES; ++r) done.gpu_per_instance[r] = eo->gpu_per_instance[r];
+    done.reservation_uid = eo->reservation_uid;
+    done.gpu_names = gpu_names_all;
+    done.xres = xres_all;
+    c->ext_reserved[pod.uid] = done;   // gs_pods_forget undoes exactly this
+  }
   apply_placement(c, pod, xo.node, true);
   if (c->host_timing)
     c->hx_reserve += std::chrono::duration<double, std::micro>(hx_clk::now() - hx3).count();
@@ -2720,22 +2757,61 @@ int gs_pods_unassign(gs_ctx* c, const uint32_t* node_idx, const gs_pod* pods, ui
 }
 
 // The scheduler cache's ForgetPod of an assumed pod after the Unreserve plugins ([upstream] scheduleOne's binding-cycle
-// failure path): NodeInfo.RemovePod, LoadAware Unreserve (podAssignCache.unAssign, load_aware.go:265-267) and
-// NodeNUMAResource Unreserve (resourceManager.Release, plugin.go:467-476).
+// failure path). A pod the extension path placed first gets the Unreserves of its recorded Reserve, in the reference's
+// order: DeviceShare (deviceshare/plugin.go:432-451 -> updateCacheUsed(..., false), device_cache.go:124-201), Reservation
+// (reservation/plugin.go:572-594 -> cache.go:175-177 -> RemoveAssignedPod, frameworkext/reservation_info.go:390-401) and
+// NodeInfo.RemovePod of the GPU-name / extended-resource scalars. Then for every pod: NodeInfo.RemovePod, LoadAware
+// Unreserve (podAssignCache.unAssign, load_aware.go:265-267) and NodeNUMAResource Unreserve (resourceManager.Release,
+// plugin.go:467-476).
 int gs_pods_forget(gs_ctx* c, const uint32_t* node_idx, const gs_pod* pods, uint32_t n) {
   if (!c || (n && (!node_idx || !pods))) return GS_EINVAL;
   quiesce(c);
-  for (uint32_t j = 0; j < n; ++j) {
+  for (uint32_t j = 0; j < n; ++j) {   // the whole call is validated before anything changes
     if (node_idx[j] >= c->N) return fail(c, GS_EINVAL, "node index %u >= %u", node_idx[j], c->N);
-    // the extension path's Reserves (DeviceShare minors and GPU-name / extended-resource requests, Reservation
-    // AddAssignedPod) have no Unreserve here: refused before anything changes
-    if (c->ext_reserved.count(pods[j].uid))
-      return fail(c, GS_EUNSUPPORTED, "gs_pods_forget: pod %llu was placed with a DeviceShare / Reservation Reserve "
-                  "(gs_schedule_ext), whose Unreserve this library does not restate", (unsigned long long)pods[j].uid);
+    if (c->ext_reserved.empty()) continue;
+    auto xt = c->ext_reserved.find(pods[j].uid);
+    if (xt != c->ext_reserved.end() && xt->second.node != node_idx[j])
+      return fail(c, GS_EINVAL, "gs_pods_forget: pod %llu was assumed on node %u, not %u",
+                  (unsigned long long)pods[j].uid, xt->second.node, node_idx[j]);
   }
   for (uint32_t j = 0; j < n; ++j) {
     const uint32_t i = node_idx[j];
     const gs_pod& p = pods[j];
+    auto xt = c->ext_reserved.empty() ? c->ext_reserved.end() : c->ext_reserved.find(p.uid);
+    if (xt != c->ext_reserved.end()) {
+      const ExtReserved& x = xt->second;
+      gs_node_devices& d = c->devs[i];
+      // DeviceShare Unreserve: SubtractWithNonNegativeResult on the minors the Device row still has (a node without a
+      // Device object now: getNodeDevice == nil, nothing to do)
+      if (d.has_device && x.gpu_minor_mask)
+        for (int g = 0; g < d.num_gpus; ++g) {
+          if (d.gpus[g].minor < 0 || d.gpus[g].minor > 31 || !(x.gpu_minor_mask >> d.gpus[g].minor & 1u)) continue;
+          for (int r = 0; r < GS_NUM_GPU_RES; ++r)
+            if (x.gpu_keys >> r & 1u)
+              d.gpus[g].used[r] = std::max<int64_t>(0, d.gpus[g].used[r] - x.gpu_per_instance[r]);
+        }
+      // Reservation Unreserve: the subtraction keeps a zero-valued key, so allocated_mask stays; a reservation deleted
+      // since is skipped (forgetPod finds no rInfo)
+      if (x.reservation_uid) {
+        auto rt = c->rsv.find(x.reservation_uid);
+        if (rt != c->rsv.end()) {
+          gs_reservation& r = rt->second;
+          for (int s = 0; s < GS_NUM_RES; ++s)
+            if (x.rsv_slots >> s & 1u) {   // (a key an upsert dropped since comes back with the value 0, as in the reference)
+              r.allocated[s] = (r.allocated_mask >> s & 1u) ? std::max<int64_t>(0, r.allocated[s] - x.rsv_added[s]) : 0;
+              r.allocated_mask |= 1u << s;
+            }
+          r.assigned_pods = std::max<int32_t>(0, r.assigned_pods - 1);
+          mark_dirty(c, r.node);   // its row carries the unmatched restore (reservation_view)
+        }
+      }
+      for (int g = 0; g < GS_NUM_GPU_NAMES; ++g)   // NodeInfo.RemovePod of the scalars
+        if (x.gpu_names >> g & 1u) d.requested[g] -= x.gpu_name_req[g];
+      for (int k = 0; k < GS_MAX_XRES; ++k)
+        if (x.xres >> k & 1u) d.xres_requested[k] -= x.xres_req[k];
+      dev_mark(c, i);
+      c->ext_reserved.erase(xt);
+    }
     HostNode& hn = c->nodes[i];
     for (int s = 0; s < GS_NUM_RES; ++s) hn.node.requested[s] -= p.requests[s];
     hn.node.nonzero_requested[0] -= p.nonzero_requests[0];
@@ -4341,6 +4417,21 @@ int gs_reservation_get(gs_ctx* c, uint64_t uid, gs_reservation* out) {
   auto it = c->rsv.find(uid);
   if (it == c->rsv.end()) return 0;
   *out = it->second;
+  return 1;
+}
+
+int gs_ext_reserved_get(gs_ctx* c, uint64_t uid, uint32_t* node, gs_ext_placement* out) {
+  if (!c || !node || !out) return GS_EINVAL;
+  quiesce(c);
+  auto it = c->ext_reserved.find(uid);
+  if (it == c->ext_reserved.end()) return 0;
+  const ExtReserved& x = it->second;
+  *node = x.node;
+  *out = gs_ext_placement{};
+  out->reservation_uid = x.reservation_uid;
+  out->gpu_minor_mask = x.gpu_minor_mask;
+  out->gpu_count = x.gpu_count;
+  for (int r = 0; r < GS_NUM_GPU_RES; ++r) out->gpu_per_instance[r] = x.gpu_per_instance[r];
   return 1;
 }
 

@@ -112,7 +112,8 @@ class Engine:
         self._chk(lib().gs_pods_unassign(self._h, abi.ptr(node_idx), abi.ptr(pods), len(pods)), "gs_pods_unassign")
 
     def forget(self, node_idx, pods):
-        """gs_pods_forget: ForgetPod of assumed pods after Unreserve (NodeInfo, podAssignCache, NUMA allocation)."""
+        """gs_pods_forget: ForgetPod of assumed pods after Unreserve (NodeInfo, podAssignCache, NUMA allocation), with
+        the DeviceShare / Reservation Unreserve of a pod schedule_ext placed (ext_reserved)."""
         node_idx = np.ascontiguousarray(node_idx, dtype=np.uint32)
         pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
         self._chk(lib().gs_pods_forget(self._h, abi.ptr(node_idx), abi.ptr(pods), len(pods)), "gs_pods_forget")
@@ -366,6 +367,15 @@ class Engine:
         self._chk(lib().gs_schedule_ext(self._h, abi.ptr(pods), abi.ptr(ext), len(pods), abi.ptr(seq), abi.ptr(out),
                                         abi.ptr(eo)), "gs_schedule_ext")
         return out, eo
+
+    def ext_reserved(self, uid: int):
+        """gs_ext_reserved_get: (node, EXT_PLACEMENT_DTYPE record) of the extension-path Reserve recorded for an
+        assumed pod, None when there is none (never placed by schedule_ext, or forgotten / unassigned since)."""
+        node = C.c_uint32(0)
+        out = np.zeros(1, abi.EXT_PLACEMENT_DTYPE)
+        rc = lib().gs_ext_reserved_get(self._h, int(uid), C.byref(node), abi.ptr(out))
+        self._chk(min(rc, 0), "gs_ext_reserved_get")
+        return (int(node.value), out[0]) if rc == 1 else None
 
     # ---- NodeNUMAResource state
     def register_topology(self, topo) -> int:

@@ -12,7 +12,10 @@ assumed pod (a PostFilter or Unreserve rejecting waiting siblings, a Permit 'Gan
 the node state under the run's later pods. At the first break the rest of the run is withdrawn (gs_pods_forget:
 NodeInfo, podAssignCache and NUMA state exactly as before those pods) and the next run starts after that pod, so every
 engine call sees the state the sequential order would. Pods left waiting at Permit can be carried to the next call
-(WaitingPods)."""
+(WaitingPods).
+
+Gangs of GPU pods and reservation pods: with `ext` (one gs_pod_ext per pod) the runs go through gs_schedule_ext; the
+withdrawals stay gs_pods_forget, which undoes the DeviceShare / Reservation Reserve the engine recorded for the pod."""
 from __future__ import annotations
 
 import ctypes as C
@@ -236,11 +239,16 @@ class _Pass:
 
 
 def schedule_with_gangs(engine, mgr: GangManager, pods, gang_ids, seq=None, nominated=None, now_ns: int = 0,
-                        run_cap: int = 192, waiting: WaitingPods | None = None):
+                        run_cap: int = 192, waiting: WaitingPods | None = None, ext=None):
     """Schedules `pods` in queue order with Coscheduling's PreFilter / Permit / PostFilter / Unreserve around every pod,
     through batched engine calls (engine: Engine or the oracle's Oracle: schedule(pods, seq), forget(nodes, pods)).
     gang_ids[i]: the pod's gang key (0: no gang). Returns (placements, result) where result holds per pod the gang
     PreFilter code, the Permit status (-1: none), the final state (ST_*) and the node it is assumed / bound on.
+
+    ext (POD_EXT_DTYPE, one record per pod): the pods' Reservation / DeviceShare inputs. Every engine call is then
+    schedule_ext(pods, ext, seq) -> (placements, ext placements) and `schedule` is not called; result["ext"] holds the
+    EXT_PLACEMENT_DTYPE record of every kept placement (zero for an unplaced or withdrawn pod). The forgets are the
+    same calls: the engine undoes the extension-path Reserve it recorded for the pod.
 
     The per-pod gate loop runs in the library (gs_gang_walk / gs_gang_replay over a gs_gang_pass): one walk and one
     replay call per engine call; this function only moves the runs through the engine and forgets withdrawn pods.
@@ -266,6 +274,17 @@ def schedule_with_gangs(engine, mgr: GangManager, pods, gang_ids, seq=None, nomi
                                            C.byref(h)), "gs_gang_pass_create")
     out = np.zeros(n, abi.PLACEMENT_DTYPE)
     out["node"] = -1
+    if ext is not None:
+        ext = np.ascontiguousarray(ext, dtype=abi.POD_EXT_DTYPE)
+        assert len(ext) == n
+    xout = np.zeros(n, abi.EXT_PLACEMENT_DTYPE)
+
+    def schedule(r):
+        """one engine call over the queue positions r: (placements, ext placements or None)"""
+        if ext is None:
+            return engine.schedule(pods[r], seq[r]), None
+        return engine.schedule_ext(pods[r], ext[r], seq[r])
+
     run = np.zeros(max(1, min(run_cap, n)), np.uint32)
     fbuf = np.zeros(n + len(waiting.pods) + 1, np.uint64)
     index = {}
@@ -298,18 +317,22 @@ def schedule_with_gangs(engine, mgr: GangManager, pods, gang_ids, seq=None, nomi
         while i < n:
             GangManager._chk(L.gs_gang_walk(h, i, run_cap, abi.ptr(run), C.byref(rn), C.byref(j)), "gs_gang_walk")
             r = run[:rn.value].astype(np.int64)
-            got = engine.schedule(pods[r], seq[r]) if len(r) else np.zeros(0, abi.PLACEMENT_DTYPE)
+            got, gx = schedule(r) if len(r) else (np.zeros(0, abi.PLACEMENT_DTYPE), None)
             got_node = np.ascontiguousarray(got["node"], np.int32)
             GangManager._chk(L.gs_gang_replay(h, i, j.value, abi.ptr(run), rn.value, abi.ptr(got_node),
                                               C.byref(r_stop), C.byref(j_next), C.byref(single)), "gs_gang_replay")
             kept = r_stop.value
             out[r[:kept]] = got[:kept]
+            if gx is not None:
+                xout[r[:kept]] = gx[:kept]
             later = kept + np.flatnonzero(got_node[kept:] >= 0)   # the run's withdrawn placements
             forget(got_node[later].astype(np.uint32), pods[r[later]])
             if single.value >= 0:   # the walk's PreFilter failed where the real one passes: this pod alone
                 k = single.value
-                one = engine.schedule(pods[k:k + 1], seq[k:k + 1])
+                one, ox = schedule(np.array([k], np.int64))
                 out[k] = one[0]
+                if ox is not None:
+                    xout[k] = ox[0]
                 GangManager._chk(L.gs_gang_pass_after_single(h, k, int(one["node"][0])), "gs_gang_pass_after_single")
                 forget(np.zeros(0, np.uint32), np.zeros(0, abi.POD_DTYPE))
             i = j_next.value
@@ -326,7 +349,11 @@ def schedule_with_gangs(engine, mgr: GangManager, pods, gang_ids, seq=None, nomi
         waiting.pods.pop(uid, None)
     for k in np.flatnonzero(state == ST_WAITING):
         waiting.pods[int(uids[k])] = (int(gang_ids[k]), int(node[k]), pods[k].copy())
-    return out, {"prefilter": prefilter, "permit": permit, "state": state, "node": node, "carried": carried}
+    res = {"prefilter": prefilter, "permit": permit, "state": state, "node": node, "carried": carried}
+    if ext is not None:
+        xout[(state == ST_REJECTED) | (out["node"] < 0)] = 0   # a rejected pod's Reserve was undone
+        res["ext"] = xout
+    return out, res
 
 
 def expire(engine, mgr: GangManager, pods, gang_ids, node, state, now_ns: int, waiting: WaitingPods | None = None):
