@@ -529,6 +529,54 @@ int gs_status_framework_code(uint16_t word);
  * ascending, up to cap; returns their count (untruncated). GS_EINVAL for a NULL row, or NULL nodes with cap > 0. */
 int gs_preemption_candidates(const uint16_t* row, uint32_t num_nodes, uint32_t* nodes, uint32_t cap);
 
+/* ---- The top-N score table of every scored pod (koord-scheduler --debug-scores N) ----
+ * frameworkext/debug.go:61-109 debugScores, called from RunScorePlugins (framework_extender.go:254-257): after a
+ * pod's Score phase, the N best feasible nodes with their totals and each plugin's weighted score. The feasible
+ * nodes arrive in feasible order (node index order here: percentageOfNodesToScore = 100), a node's total is the sum
+ * of the weighted plugin scores, and the nodes are sorted by total descending.
+ * Fixed order: the reference sorts with sort.Slice, which is not stable, so among nodes of equal total neither the
+ * order nor which of them make the cut is defined there. Here the remaining tie is ascending node index, in the
+ * order and at the cut: rows are sorted by (total descending, node ascending).
+ * No table: [upstream] schedulePod returns before prioritizeNodes when exactly one node is feasible, and a pod with
+ * no feasible node never reaches it, so a pod with 0 or 1 feasible nodes has count 0 (although the latter is
+ * placed); a pod with 2 <= feasible < topn has `feasible` rows. */
+#define GS_MAX_TOP_SCORES 64          /* one wave's lanes */
+typedef struct gs_top_score {          /* 12 B */
+  uint32_t node;
+  int16_t  total;                      /* weighted total, what gs_evaluate's scores[] holds */
+  int16_t  plugin[GS_NUM_PLUGINS];     /* UNweighted, as gs_evaluate's plugin_scores[] */
+} gs_top_score;
+typedef struct gs_top_scores {
+  gs_top_score* rows;                  /* in: [npods][topn], caller-owned, valid like out[] */
+  uint32_t*     count;                 /* in: [npods]; out: rows filled for pod i (0: no table) */
+  uint32_t      topn;                  /* in: 1..GS_MAX_TOP_SCORES */
+} gs_top_scores;
+/* gs_schedule / gs_schedule_submit with the tables: out[] is bit for bit what the plain call writes;
+ * rows[i*topn .. i*topn + count[i]) is pod i's table at pod i's turn (after every earlier placement of the call,
+ * before its own and any later one), sorted by (total descending, node ascending); total = sum over the plugins of
+ * gs_config.plugin_weights[k] * plugin[k]. Nothing past count[i] in a pod's rows is written, and nothing outside the
+ * two arrays. Scope: one rank, no node sampling (the reference then scores the rotation window only), no extension
+ * pods (gs_schedule_ext): with several ranks or node sampling both calls return GS_EUNSUPPORTED before anything is
+ * scheduled. A NULL struct, rows or count, or topn outside 1..GS_MAX_TOP_SCORES: GS_EINVAL. The struct and its
+ * arrays must stay valid like out (a submission: until gs_schedule_wait returns). A context that never makes these
+ * calls allocates and launches nothing for them. */
+int gs_schedule_top_scores(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                           gs_top_scores* top);
+int gs_schedule_submit_top_scores(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint64_t* seq,
+                                  gs_placement* out, gs_top_scores* top, uint64_t* ticket);   /* gs_schedule_wait */
+/* debugScores itself (frameworkext/debug.go:61-109; pinned by debug_test.go TestDebugScores), as a pure host
+ * function: the go-pretty RenderMarkdown text of the table. pod_ref is klog.KObj(pod) ("namespace/name");
+ * node_names[n_nodes] the feasible nodes in feasible order; plugin_names[n_plugins]; scores[p * n_nodes + n] the
+ * WEIGHTED score of plugin p on node n. A node's total is the sum over the plugins; the nodes are sorted by (total
+ * descending, input order ascending: the fixed order above) and cut at topn; the plugin columns are sorted by name
+ * bytewise (sort.Strings). The text is a header line, a separator line ("---" for the columns #, Pod and Node,
+ * "---:" for every numeric column) and one line per row, joined by "\n" with no trailing newline. Names are copied
+ * verbatim: DNS-1123 names never hold '|' or a newline, and nothing is escaped. Written to buf NUL-terminated,
+ * truncated to len; returns the untruncated length, GS_EINVAL for topn < 0 or a NULL array that is needed. */
+int gs_debug_scores_string(int topn, const char* pod_ref, const char* const* node_names, uint32_t n_nodes,
+                           const char* const* plugin_names, uint32_t n_plugins, const int64_t* scores, char* buf,
+                           size_t len);
+
 /* ---- NodeNUMAResource state ---- */
 /* Register a CPUTopology; returns its id in *id (identical topologies may share one id). */
 int gs_topology_register(gs_ctx* ctx, const gs_cpu_topology* topo, int32_t* id);

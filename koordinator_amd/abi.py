@@ -412,6 +412,47 @@ class GsGangInfo(C.Structure):
                                    "pad")] + [("wait_time_ns", i64)]
 
 
+class GsTopScore(C.Structure):
+    _fields_ = [("node", u32), ("total", C.c_int16), ("plugin", C.c_int16 * GS_NUM_PLUGINS)]
+
+
+class GsTopScores(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("count", C.c_void_p), ("topn", u32)]
+
+
+GS_MAX_TOP_SCORES = 64
+# the score plugins of a gs_top_score row: (index in plugin[] and gs_config.plugin_weights, gs_config.enabled bit, name)
+SCORE_PLUGINS = ((GS_PLUGIN_FIT, GS_ENABLE_FIT_SCORE, "NodeResourcesFit"),
+                 (GS_PLUGIN_LOADAWARE, GS_ENABLE_LA_SCORE, "LoadAwareScheduling"),
+                 (GS_PLUGIN_NUMA, GS_ENABLE_NUMA_SCORE, "NodeNUMAResource"))
+
+
+def debug_scores_string(topn: int, pod_ref: str, node_names, plugin_names, scores) -> str:
+    """gs_debug_scores_string: frameworkext/debug.go debugScores' markdown table. scores[plugin][node]: weighted."""
+    sc = np.ascontiguousarray(scores, dtype=np.int64).reshape(len(plugin_names), len(node_names))
+    nn = (C.c_char_p * max(1, len(node_names)))(*[n.encode() for n in node_names])
+    pn = (C.c_char_p * max(1, len(plugin_names)))(*[n.encode() for n in plugin_names])
+    args = (int(topn), pod_ref.encode(), nn, len(node_names), pn, len(plugin_names), ptr(sc))
+    n = load().gs_debug_scores_string(*args, None, 0)
+    if n < 0:
+        raise ValueError(f"gs_debug_scores_string: {n}")
+    buf = C.create_string_buffer(n + 1)
+    load().gs_debug_scores_string(*args, buf, len(buf))
+    return buf.value.decode()
+
+
+def debug_scores_table(rows, cfg, pod_ref: str, node_names) -> str:
+    """The --debug-scores table of one pod from its gs_top_score rows (TOP_SCORE_DTYPE, already sorted and cut):
+    a column per enabled score plugin of cfg (a GsConfig) holding plugin x weight, as RunScorePlugins leaves them.
+    node_names: the name of every node of the cluster, by node index."""
+    cols = [(k, name) for k, bit, name in SCORE_PLUGINS if cfg.enabled & bit]
+    names = [node_names[int(n)] for n in rows["node"]]
+    sc = np.zeros((len(cols), len(rows)), np.int64)
+    for j, (k, _) in enumerate(cols):
+        sc[j] = rows["plugin"][:, k].astype(np.int64) * int(cfg.plugin_weights[k])
+    return debug_scores_string(len(rows), pod_ref, names, [name for _, name in cols], sc)
+
+
 MERGE_CASE_DTYPE = np.dtype(GsMergeCase)
 MERGE_RESULT_DTYPE = np.dtype(GsMergeResult)
 POD_DTYPE = np.dtype(GsPod)
@@ -420,6 +461,7 @@ METRIC_DTYPE = np.dtype(GsNodeMetric)
 POD_METRIC_DTYPE = np.dtype(GsPodMetric)
 PLACEMENT_DTYPE = np.dtype(GsPlacement)
 FIT_DIAGNOSIS_DTYPE = np.dtype(GsFitDiagnosis)
+TOP_SCORE_DTYPE = np.dtype(GsTopScore)
 TOPOLOGY_DTYPE = np.dtype(GsCpuTopology)
 NODE_NUMA_DTYPE = np.dtype(GsNodeNuma)
 POD_ALLOCATION_DTYPE = np.dtype(GsPodAllocation)
@@ -449,6 +491,7 @@ STRUCT_SIZES = {
     "gs_preempt_candidate": C.sizeof(GsPreemptCandidate),
     "gs_preempt_result_pdb": C.sizeof(GsPreemptResultPdb), "gs_preempt_detail_pdb": C.sizeof(GsPreemptDetailPdb),
     "gs_preempt_candidate_pdb": C.sizeof(GsPreemptCandidatePdb),
+    "gs_top_score": C.sizeof(GsTopScore), "gs_top_scores": C.sizeof(GsTopScores),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -479,6 +522,9 @@ SIGNATURES = {
     "gs_fit_error_string": (C.c_int, [P, P, C.c_char_p, C.c_size_t]),
     "gs_schedule_diag_nodes": (C.c_int, [P, P, u32, P, P, P, C.POINTER(GsStatusMap)]),
     "gs_schedule_submit_diag_nodes": (C.c_int, [P, P, u32, P, P, P, C.POINTER(GsStatusMap), C.POINTER(u64)]),
+    "gs_schedule_top_scores": (C.c_int, [P, P, u32, P, P, C.POINTER(GsTopScores)]),
+    "gs_schedule_submit_top_scores": (C.c_int, [P, P, u32, P, P, C.POINTER(GsTopScores), C.POINTER(u64)]),
+    "gs_debug_scores_string": (C.c_int, [C.c_int, C.c_char_p, P, u32, P, u32, P, C.c_char_p, C.c_size_t]),
     "gs_status_framework_code": (C.c_int, [C.c_uint16]),
     "gs_preemption_candidates": (C.c_int, [P, u32, P, u32]),
     "gs_comm_unique_id": (C.c_int, [P]),

@@ -9,7 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libgpuscore.so")
 SOURCES = ["gs_engine.cpp", "gs_numa_host.cpp", "gs_ingest.cpp", "gs_quota.cpp", "gs_gang.cpp", "gs_reasons.cpp",
-           "gs_preempt.cpp", "gs_kernels.hip", "gs_fit_diag.hip", "gs_preempt.hip",
+           "gs_preempt.cpp", "gs_debug_scores.cpp", "gs_kernels.hip", "gs_fit_diag.hip", "gs_top_scores.hip",
+           "gs_preempt.hip",
            "gs_commit_spec.hip", "gs_probe.hip", "gs_ext.hip"]
 OBJ = os.path.join(HERE, "build")
 # host code off the per-pod path whose -O3 build takes minutes in clang (the inlined cpuset selection of the

@@ -122,6 +122,12 @@ struct Slot {
   bool rows_in_flight = false;      // ev_rows is recorded and no later pass has waited for it yet
   DevBuf<uint16_t> d_lwords;        // [pod of the landed pass][landed node]: the landed pass's words
   PinnedBuf<uint16_t> h_lwords;
+  // the top-N score tables (gs_schedule_top_scores; allocated by the context's first such run, alloc_top)
+  uint32_t top_n = 0;               // > 0: the slot's batch runs top_scores_kernel behind its commit, with this topn
+  DevBuf<uint8_t> d_top;            // the pass's counts and rows (TOP_BYTES), read back with the placements
+  PinnedBuf<uint8_t> h_top;
+  DevBuf<TopLanded> d_ltop;         // [pod of the landed pass][landed node]: the landed pass's totals and plugin scores
+  PinnedBuf<TopLanded> h_ltop;
 };
 
 // The ElasticQuota PostFilter dry run (gs_preempt_dry_run): the resident-pod table with its device image and the dry
@@ -162,6 +168,7 @@ struct AsyncRun {
   gs_placement* out = nullptr;
   gs_fit_diagnosis* diag = nullptr;   // gs_schedule_submit_diag
   gs_status_map* map = nullptr;       // gs_schedule_submit_diag_nodes
+  gs_top_scores* top = nullptr;       // gs_schedule_submit_top_scores
   uint64_t ticket = 0;
   int rc = 1;   // 1: not complete
   std::string err;
@@ -325,6 +332,9 @@ struct gs_ctx {
   double hd_derive = 0, hd_landed = 0;
   uint64_t hd_batches = 0, hd_versions = 0, hd_pods = 0;
   uint64_t hd_map_rows = 0, hd_map_bytes = 0;   // status map: rows read back, and their bytes with the landed words'
+  // ... and of the top-N score tables: deriving the landed-row versions, the landed pass, merging into the caller's rows
+  double tp_derive = 0, tp_landed = 0, tp_merge = 0;
+  uint64_t tp_batches = 0, tp_versions = 0, tp_pods = 0;
   // ... and of gs_schedule_ext: per extension pod (records, flushes, the device chain up to the host's wake-up, the
   // Reserves) and per plain run (the whole gs_schedule call)
   double hx_prep = 0, hx_flush = 0, hx_gpu = 0, hx_reserve = 0, hx_plain = 0;
@@ -1452,6 +1462,75 @@ int alloc_map(gs_ctx* c) {
   return GS_OK;
 }
 
+// the buffers of the top-N score tables, on the context's first run that asks for them (after alloc_diag: the landed
+// pass shares the diagnosis' staged block, slab and stream)
+int alloc_top(gs_ctx* c) {
+  if (c->slot[0].d_top) return GS_OK;
+  HIP_TRY(c, hipSetDevice(c->cfg.device));
+  const size_t lt = sizeof(TopLanded) * MAX_BATCH * MAX_BATCH;
+  for (Slot& s : c->slot) {
+    HIP_TRY(c, s.h_top.alloc(TOP_BYTES));
+    HIP_TRY(c, s.d_ltop.alloc(lt));
+    HIP_TRY(c, s.h_ltop.alloc(lt));
+    HIP_TRY(c, s.d_top.alloc(TOP_BYTES));
+    // the read-back path has run once before a batch is in flight (its first use costs the host milliseconds)
+    HIP_TRY(c, hipMemsetAsync(s.d_top.get(), 0, TOP_BYTES, c->st_dg.get()));
+    HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_BYTES, hipMemcpyDeviceToHost, c->st_dg.get()));
+  }
+  HIP_TRY(c, host_wait_stream(c->st_dg.get()));
+  HIP_TRY(c, preload_top_scores());
+  return GS_OK;
+}
+
+TopArgs top_args(const gs_ctx* c, const Slot& s, int b) {
+  TopArgs a{};
+  a.m = c->mv;
+  a.pods = s.d_pods.get();
+  a.pf = c->pf;
+  a.N = c->N;
+  a.npods = b;
+  a.committed = s.d_committed.get();
+  a.out = s.d_out;
+  a.S = s.d_S.get();
+  a.ld = c->ld;
+  a.topn = s.top_n;
+  a.nbins = c->max_score + 1;
+  a.top = s.d_top.get();
+  return a;
+}
+
+// The landed pass of a batch's tables (blocking; off the commit stream), as diag_landed: nv row versions staged at
+// the head of s.h_dgl are scattered into the slot's slab, pod f (fpods[f]) is evaluated on versions vidx[f * nL ..],
+// and the nF x nL totals and plugin scores arrive in s.h_ltop.
+int top_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL) {
+  const int nF = (int)fpods.size();
+  const size_t off_idx = (size_t)nv * ROW_WORDS * 8;
+  const size_t off_pods = (off_idx + (size_t)nv * 4 + 7) & ~(size_t)7;
+  const size_t off_vidx = off_pods + sizeof(PodVec) * nF;
+  const size_t total = off_vidx + 2 * (size_t)nF * nL;
+  if (nv > DIAG_VERSIONS || total > DGL_BYTES) return fail(c, GS_ESTATE, "top scores: landed-row versions overflow");
+  uint8_t* h = s.h_dgl.get();
+  uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + off_idx);
+  for (int v = 0; v < nv; ++v) h_idx[v] = (uint32_t)v;
+  std::memcpy(h + off_pods, fpods.data(), sizeof(PodVec) * nF);
+  std::memcpy(h + off_vidx, vidx.data(), 2 * (size_t)nF * nL);
+  const hipStream_t st = c->st_dg.get();
+  uint8_t* d = s.d_dgl.get();
+  const MirrorView slab{s.dgl_i64.get(), s.dgl_i32.get(), (uint32_t)DIAG_VERSIONS};
+  const gs_loadaware_args& la = c->cfg.loadaware;
+  const ScatterPrep sp{c->now, la.filter_expired_node_metrics, la.has_node_metric_expiration,
+                       la.has_node_metric_expiration ? la.node_metric_expiration_seconds * 1000000000LL : 0};
+  HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, launch_scatter_rows(slab, reinterpret_cast<const uint32_t*>(d + off_idx), reinterpret_cast<const int64_t*>(d),
+                                 (uint32_t)nv, st, &sp));
+  HIP_TRY(c, launch_top_scores_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
+                                      reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ltop.get(), st));
+  HIP_TRY(c, hipMemcpyAsync(s.h_ltop.get(), s.d_ltop.get(), sizeof(TopLanded) * nF * nL, hipMemcpyDeviceToHost, st));
+  Where w_(c, "top_landed: the landed pass");
+  HIP_TRY(c, host_wait_stream(st));
+  return GS_OK;
+}
+
 DiagMapArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
   DiagMapArgs a{};
   a.m = c->mv;
@@ -1521,8 +1600,9 @@ int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, co
 // its commit kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
 // diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements; map: the
 // pass also leaves the status rows in the slot's d_words (fetch_rows reads back the ones the caller has room for).
+// topn > 0: the top-N score tables' pass behind the commit instead, its counts and rows read back with the placements.
 int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0, bool diag = false,
-                 bool map = false) {
+                 bool map = false, uint32_t topn = 0) {
   const int32_t* prev = before ? before->d_committed.get() : nullptr;
   const PlacementDev* prev_out = before ? before->d_out : nullptr;
   const hipStream_t st = c->st.get(), st_ev = c->st_ev.get();
@@ -1659,9 +1739,17 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
     HIP_TRY(c, hipStreamWaitEvent(st, s.ev_rows.get(), 0));
     s.rows_in_flight = false;
   }
+  s.top_n = topn;
   if (diag) {   // behind the commit's write-back, before the next batch's fix-up and commit (stream order)
     HIP_TRY(c, hipMemsetAsync(s.d_diag.get(), 0, DIAG_BYTES, st));
     HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));
+    if (rb != st) {
+      HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
+      HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
+    }
+  }
+  if (topn) {   // the same place: the mirror holds the commit's write-back, the slot's score rows are still the batch's
+    HIP_TRY(c, launch_top_scores(top_args(c, s, b), st));
     if (rb != st) {
       HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
       HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
@@ -1674,6 +1762,8 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
   HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
   if (diag)
     HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * b, hipMemcpyDeviceToHost, rb));
+  if (topn)
+    HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_COUNT_BYTES + TOP_POD_BYTES * b, hipMemcpyDeviceToHost, rb));
   HIP_TRY(c, hipEventRecord(s.ev[5].get(), rb));
   return GS_OK;
 }
@@ -1784,6 +1874,7 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     HIP_TRY(c, launch_commit(a, st));
     HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
     if (s.diag_on) HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));   // (the first pass committed nothing: counters 0)
+    if (s.top_n) HIP_TRY(c, launch_top_scores(top_args(c, s, b), st));         // (... and wrote no table)
     HIP_TRY(c, hipMemcpyAsync(h_committed, s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
     c->stats.commit_ms += ev_ms(s.ev[3].get(), s.ev[4].get());
@@ -1792,6 +1883,9 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * committed, hipMemcpyDeviceToHost, st));
     if (s.diag_on)
       HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * committed,
+                                hipMemcpyDeviceToHost, st));
+    if (s.top_n)
+      HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_COUNT_BYTES + TOP_POD_BYTES * committed,
                                 hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
   }
@@ -2340,7 +2434,8 @@ void gs_abi_sizes(uint64_t* out, uint32_t n) {
                         sizeof(gs_reservation), sizeof(gs_pod_ext), sizeof(gs_ext_args), sizeof(gs_ext_placement),
                         sizeof(gs_status_map), sizeof(gs_resident_pod), sizeof(gs_preemptor),
                         sizeof(gs_preempt_result), sizeof(gs_preempt_detail), sizeof(gs_preempt_candidate),
-                        sizeof(gs_preempt_result_pdb), sizeof(gs_preempt_detail_pdb), sizeof(gs_preempt_candidate_pdb)};
+                        sizeof(gs_preempt_result_pdb), sizeof(gs_preempt_detail_pdb), sizeof(gs_preempt_candidate_pdb),
+                        sizeof(gs_top_score), sizeof(gs_top_scores)};
   for (uint32_t i = 0; i < n && i < sizeof(s) / sizeof(s[0]); ++i) out[i] = s[i];
 }
 
@@ -2554,6 +2649,13 @@ void report_host_timing(const gs_ctx* c) {
     if (c->hd_map_rows)
       fprintf(stderr, "gpuscore status map: %llu rows read back, %.0f bytes device-to-host per such batch\n",
               (unsigned long long)c->hd_map_rows, (double)c->hd_map_bytes / n);
+  }
+  if (c->host_timing && c->tp_batches) {
+    const double n = (double)c->tp_batches;
+    fprintf(stderr, "gpuscore top scores, host per batch with a scored pod (us, %llu batches, %llu pods, %llu landed-row "
+            "versions): deriving the versions %.1f | landed pass, upload to rows %.1f | merge %.1f\n",
+            (unsigned long long)c->tp_batches, (unsigned long long)c->tp_pods, (unsigned long long)c->tp_versions,
+            c->tp_derive / n, c->tp_landed / n, c->tp_merge / n);
   }
 }
 
@@ -2957,6 +3059,8 @@ struct PodRun {
   void* tag = nullptr;
   gs_fit_diagnosis* diag = nullptr;   // gs_schedule_diag: the FitError diagnosis of each pod (else none is computed)
   gs_status_map* map = nullptr;       // gs_schedule_diag_nodes: the per-node status rows of those pods (with diag)
+  gs_top_scores* top = nullptr;       // gs_schedule_top_scores: the top-N score table of each scored pod
+  uint32_t topn() const { return top ? top->topn : 0u; }
   // whether the run's batches run the wide pass with the status rows (a map without rows keeps the counters-only kernels)
   bool wants_rows() const { return map && map->cap_rows; }
 };
@@ -3010,9 +3114,107 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
   std::vector<uint8_t> dg_stale;
   std::vector<PodVec> dg_pods;
   std::vector<int> dg_k;
+  // The batch's top-N score tables into tp's rows and counts of the run's pods [base, base + n). topblk: the device
+  // pass's block of the batch (per pod the first topn of the nodes the batch did not land on, sorted). The landed
+  // nodes are added here, as the diagnosis adds them: walking the placements in queue order, at every scored pod
+  // (placed, and more than one node feasible: [upstream] schedulePod skips prioritizeNodes otherwise) the host state
+  // of every node is its state at that pod's turn, before its own landing, so the landed nodes' row versions are
+  // derived there and evaluated by the landed pass; a feasible landed node joins the pod's list, which is sorted by
+  // (total descending, node ascending) and cut at topn. The top-N of the union lies within the device's top-N of the
+  // other nodes and the landed ones.
+  std::vector<gs_top_score> tp_rows;
+  auto apply_batch_top = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
+                             bool special, Slot* sl, uint32_t base, gs_top_scores* tp, const uint8_t* topblk) -> int {
+    int nv = 0;
+    dg_nodes.clear();
+    for (int k = 0; k < n; ++k)
+      if (hout[k].node >= 0 && std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)hout[k].node) == dg_nodes.end())
+        dg_nodes.push_back((uint32_t)hout[k].node);
+    const int nL = (int)dg_nodes.size();
+    dg_cur.assign(nL, 0);
+    dg_stale.assign(nL, 1);
+    dg_vidx.clear();
+    dg_pods.clear();
+    dg_k.clear();
+    double t_derive = 0;
+    for (int k = 0; k < n; ++k) {
+      const PlacementDev& pd = hout[k];
+      gs_placement& o = outp[k];
+      o.node = pd.node;
+      o.feasible = pd.feasible;
+      o.score = pd.node >= 0 ? pd.score : 0;
+      o.ties = pd.node >= 0 ? pd.ties : 0;
+      o.flags = pd.flags & ~PL_INTERNAL_FLAGS;
+      if (pd.flags & GS_PLACED_SLOWPATH) c->stats.slowpath_pods += 1;
+      tp->count[base + k] = 0;
+      if (pd.node >= 0 && pd.feasible >= 2) {
+        const int64_t t0 = c->host_timing ? mono_ns() : 0;
+        for (int j = 0; j < nL; ++j) {
+          if (dg_stale[j]) {
+            if (nv >= DIAG_VERSIONS) return fail(c, GS_ESTATE, "top scores: landed-row versions overflow");
+            int64_t* row = reinterpret_cast<int64_t*>(sl->h_dgl.get()) + (size_t)nv * ROW_WORDS;
+            derive_row(c, dg_nodes[j], row);
+            derive_row_numa(c, dg_nodes[j], row);
+            dg_cur[j] = (uint16_t)nv++;
+            dg_stale[j] = 0;
+          }
+          dg_vidx.push_back(dg_cur[j]);
+        }
+        dg_pods.push_back(hpods[k]);
+        dg_k.push_back(k);
+        if (c->host_timing) t_derive += (double)(mono_ns() - t0) * 1e-3;
+      }
+      if (int rc = numa_reserve(c, pods[k], hpods[k], pd)) return rc;
+      apply_placement(c, pods[k], pd.node, special);
+      if (pd.node >= 0) dg_stale[std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)pd.node) - dg_nodes.begin()] = 1;
+    }
+    if (dg_k.empty()) return GS_OK;
+    const int64_t t1 = c->host_timing ? mono_ns() : 0;
+    if (int rc = top_landed(c, *sl, nv, dg_pods, dg_vidx, nL)) return rc;   // (a scored pod landed: nL >= 1)
+    const uint32_t* dcnt = reinterpret_cast<const uint32_t*>(topblk);
+    const gs_top_score* drows = reinterpret_cast<const gs_top_score*>(topblk + TOP_COUNT_BYTES);
+    const TopLanded* landed = sl->h_ltop.get();
+    const int64_t t2 = c->host_timing ? mono_ns() : 0;
+    for (size_t f = 0; f < dg_k.size(); ++f) {
+      const int k = dg_k[f];
+      const uint32_t dn = dcnt[k];
+      if (dn > tp->topn) return fail(c, GS_ESTATE, "top scores: the device pass wrote no table for a scored pod");
+      tp_rows.assign(drows + (size_t)k * GS_MAX_TOP_SCORES, drows + (size_t)k * GS_MAX_TOP_SCORES + dn);
+      // (the device's list is full and sorted: a landed node behind its last row cannot make the cut)
+      const bool full = dn == tp->topn;
+      const gs_top_score last = full ? tp_rows.back() : gs_top_score{};
+      for (int j = 0; j < nL; ++j) {
+        const TopLanded& l = landed[f * nL + j];
+        if (l.total < 0) continue;
+        if (full && (l.total < last.total || (l.total == last.total && dg_nodes[j] > last.node))) continue;
+        gs_top_score r;
+        r.node = dg_nodes[j];
+        r.total = l.total;
+        for (int q = 0; q < GS_NUM_PLUGINS; ++q) r.plugin[q] = l.plugin[q];
+        tp_rows.push_back(r);
+      }
+      std::sort(tp_rows.begin(), tp_rows.end(), [](const gs_top_score& a, const gs_top_score& b) {
+        return a.total > b.total || (a.total == b.total && a.node < b.node);
+      });
+      const uint32_t cnt = std::min<uint32_t>((uint32_t)tp_rows.size(), tp->topn);
+      std::memcpy(tp->rows + (size_t)(base + k) * tp->topn, tp_rows.data(), sizeof(gs_top_score) * cnt);
+      tp->count[base + k] = cnt;
+    }
+    if (c->host_timing) {
+      c->tp_derive += t_derive;
+      c->tp_landed += (double)(t2 - t1) * 1e-3;
+      c->tp_merge += (double)(mono_ns() - t2) * 1e-3;
+      c->tp_batches += 1;
+      c->tp_versions += nv;
+      c->tp_pods += dg_k.size();
+    }
+    return GS_OK;
+  };
   auto apply_batch = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
                          bool special, gs_fit_diagnosis* dg = nullptr, const uint32_t* wide = nullptr,
-                         Slot* sl = nullptr, gs_status_map* mp = nullptr, uint32_t base = 0) -> int {
+                         Slot* sl = nullptr, gs_status_map* mp = nullptr, uint32_t base = 0,
+                         gs_top_scores* tp = nullptr, const uint8_t* topblk = nullptr) -> int {
+    if (tp) return apply_batch_top(pods, outp, n, hout, hpods, special, sl, base, tp, topblk);
     int nfit = 0, nv = 0, nrow = 0;
     if (mp)
       for (int k = 0; k < n; ++k) mp->row_of[base + k] = -1;
@@ -3123,7 +3325,9 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     Slot* slot = nullptr;   // the slot the batch ran on (its landed-pass buffers)
     gs_status_map* map = nullptr;
     uint32_t base = 0;
+    gs_top_scores* top = nullptr;
   } pend;
+  std::vector<uint8_t> pend_top;
   std::vector<PlacementDev> pend_out;
   std::vector<PodVec> pend_pods;
   std::vector<uint32_t> pend_wide;
@@ -3151,7 +3355,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     if (!pend.active) return GS_OK;
     pend.active = false;
     return apply_batch(pend.pods, pend.out, pend.n, pend_out.data(), pend_pods.data(), false, pend.diag,
-                       pend_wide.data(), pend.slot, pend.map, pend.base);
+                       pend_wide.data(), pend.slot, pend.map, pend.base, pend.top, pend_top.data());
   };
   auto body = [&]() -> int {
     int rc = GS_OK;
@@ -3180,7 +3384,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         cur_b = batch_len(c, pods, i, run.n, &cur_special);
         // (a cpuset pod whose node is outside the device cpuset scope ends the batch inside the commit kernel)
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows()))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows(), run.topn()))) return rc;
       }
       // the batch after this one: in this run, or the first of the next run
       const gs_pod* np = nullptr;
@@ -3189,13 +3393,14 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       const uint32_t j = i + cur_b;
       bool ndiag = run.diag != nullptr;   // whether the batch after this one is diagnosed (its own run's choice)
       bool nmap = run.wants_rows();
+      uint32_t ntop = run.topn();
       if (j < run.n) {
         np = pods; ns = run.seq; nj = j; nn = run.n;
       } else {
         if (!have_nxt) have_nxt = next_run(&nxt);
         bool use = have_nxt && nxt.n;
         if (c->nranks > 1 && (rc = agree_next_run(c, &use))) { drain(); return rc; }
-        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; nmap = nxt.wants_rows(); }
+        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; nmap = nxt.wants_rows(); ntop = nxt.topn(); }
       }
       bool spec = false;
       int nb = 0;
@@ -3212,7 +3417,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         if (!sf && !uid_overlap(pods + i, cur_b, np + nj, nb)) {
           rc = stage_batch(c, ahead, np, ns, nj, nb, true);
           const auto t_b = hclk::now();
-          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag, nmap);
+          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag, nmap, ntop);
           if (c->host_timing) {
             const double st = std::chrono::duration<double, std::micro>(t_b - t_a).count();
             const double la = std::chrono::duration<double, std::micro>(hclk::now() - t_b).count();
@@ -3235,7 +3440,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         drain();
         if ((rc = apply_pending())) return rc;
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows()))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows(), run.topn()))) return rc;
         inflight = true;
         spec_ok = false;
         continue;
@@ -3261,9 +3466,12 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         pend.slot = &cur;
         pend.map = run.map;
         pend.base = i;
+        pend.top = run.top;
         if (run.diag) pend_wide.assign(cur.h_diag.get(), cur.h_diag.get() + (size_t)DIAG_WORDS * committed);
+        if (run.top) pend_top.assign(cur.h_top.get(), cur.h_top.get() + TOP_COUNT_BYTES + TOP_POD_BYTES * committed);
       } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special,
-                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur, run.map, i))) {
+                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur, run.map, i, run.top,
+                                   cur.h_top.get()))) {
         if (spec) drain();
         return rc;
       }
@@ -3333,6 +3541,7 @@ void async_worker(gs_ctx* c) {
       p.out = r->out;
       p.diag = r->diag;
       p.map = r->map;
+      p.top = r->top;
       p.n = (uint32_t)r->pods.size();
       p.tag = r.get();
       return p;
@@ -3400,7 +3609,7 @@ int diag_supported(gs_ctx* c) {
 }
 
 int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                 gs_fit_diagnosis* diag, gs_status_map* map = nullptr) {
+                 gs_fit_diagnosis* diag, gs_status_map* map = nullptr, gs_top_scores* top = nullptr) {
   int rc = ready(c);
   if (rc) return rc;
   for (uint32_t i = 0; i < npods; ++i)
@@ -3412,12 +3621,13 @@ int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* 
   run.n = npods;
   run.diag = diag;
   run.map = map;
+  run.top = top;
   return schedule_stream(c, run, [](PodRun*) { return false; }, [](const PodRun&, int) {});
 }
 
 // gs_schedule_submit: the run copied and queued for the worker
 int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-               gs_fit_diagnosis* diag, uint64_t* ticket, gs_status_map* map = nullptr) {
+               gs_fit_diagnosis* diag, uint64_t* ticket, gs_status_map* map = nullptr, gs_top_scores* top = nullptr) {
   auto r = std::make_shared<AsyncRun>();
   // checks that write nothing (the worker may be running): on an error, wait for it, then report
   if (c->n_valid != c->N) {
@@ -3438,6 +3648,7 @@ int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* se
   r->out = out;
   r->diag = diag;
   r->map = map;
+  r->top = top;
   if (!c->aq) {
     c->aq = std::make_unique<AsyncQueue>();
     c->aq->th = std::thread(async_worker, c);
@@ -3516,6 +3727,41 @@ int gs_schedule_submit_diag_nodes(gs_ctx* c, const gs_pod* pods, uint32_t npods,
     if (int rc = alloc_map(c)) return rc;
   }
   return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket, npods ? map : nullptr);
+}
+
+namespace {
+// the scope of the top-N score tables: that of the diagnosis (under node sampling the reference scores only the
+// rotation window)
+int top_supported(gs_ctx* c) {
+  if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "top scores: several ranks are not supported");
+  if (c->window_k) return fail(c, GS_EUNSUPPORTED, "top scores: node sampling is not supported");
+  return GS_OK;
+}
+bool top_valid(const gs_top_scores* t) {
+  return t && t->rows && t->count && t->topn >= 1 && t->topn <= GS_MAX_TOP_SCORES;
+}
+}  // namespace
+
+int gs_schedule_top_scores(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                           gs_top_scores* top) {
+  if (!c || (npods && (!pods || !out)) || !top_valid(top)) return GS_EINVAL;
+  quiesce(c);
+  if (int rc = top_supported(c)) return rc;
+  if (int rc = alloc_diag(c)) return rc;
+  if (int rc = alloc_top(c)) return rc;
+  return schedule_run(c, pods, npods, seq, out, nullptr, nullptr, npods ? top : nullptr);
+}
+
+int gs_schedule_submit_top_scores(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                                  gs_top_scores* top, uint64_t* ticket) {
+  if (!c || !ticket || (npods && (!pods || !out)) || !top_valid(top)) return GS_EINVAL;
+  if (c->nranks > 1 || c->window_k || !c->st_dg || !c->slot[0].d_top) {
+    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
+    if (int rc = top_supported(c)) return rc;
+    if (int rc = alloc_diag(c)) return rc;
+    if (int rc = alloc_top(c)) return rc;
+  }
+  return submit_run(c, pods, npods, seq, out, nullptr, ticket, nullptr, npods ? top : nullptr);
 }
 
 int gs_status_framework_code(uint16_t word) { return gs_reason_string(GS_STATUS_CODE(word), 0, nullptr, nullptr, 0); }

@@ -272,6 +272,41 @@ hipError_t preload_fit_diag_map();
 hipError_t launch_fit_diag_landed_map(const MirrorView& slab, const PodVec* pods, const Profile& pf, const uint16_t* vidx,
                                       int nF, int nL, uint32_t* out, uint16_t* words, hipStream_t st);
 
+// ---- the top-N score tables (gs_top_scores.hip; gs_schedule_top_scores) ----
+// The pass's output block: TOP_COUNT_BYTES of per-pod counts, then per pod GS_MAX_TOP_SCORES gs_top_score rows.
+constexpr size_t TOP_COUNT_BYTES = sizeof(uint32_t) * MAX_BATCH;
+constexpr size_t TOP_POD_BYTES = sizeof(gs_top_score) * GS_MAX_TOP_SCORES;
+constexpr size_t TOP_BYTES = TOP_COUNT_BYTES + TOP_POD_BYTES * MAX_BATCH;
+struct TopArgs {
+  MirrorView m;
+  const PodVec* pods;        // the batch's pod vectors
+  Profile pf;
+  uint32_t N;                // nodes (the rows' padding is never read as a node)
+  int npods;                 // pods of the pass
+  const int32_t* committed;  // the pass's committed words ([0]: pods committed; a voided pass: -1)
+  const PlacementDev* out;   // its placements
+  const int16_t* S;          // the batch's score rows [pod][ld]
+  uint32_t ld;
+  uint32_t topn;             // 1..GS_MAX_TOP_SCORES
+  int nbins;                 // the profile's highest total + 1 (<= MAX_SCORE_LIMIT + 1): the histogram's bins
+  uint8_t* top;              // the output block (TOP_BYTES)
+};
+// Behind a batch's commit, on its stream: workgroup p writes, for committed pod p, the first topn of the nodes the
+// batch's committed pods did not land on by (S[p][node] descending, node ascending) — the row holds such a node's
+// total at the pod's turn — each with its three plugin scores from the node's mirror row, and their count. Does
+// nothing for a voided pass.
+hipError_t launch_top_scores(const TopArgs& a, hipStream_t st);
+struct TopLanded {           // one (pod, landed-row version) pair
+  int16_t total;             // weighted total, -1: infeasible
+  int16_t plugin[GS_NUM_PLUGINS];
+};
+// The landed rows: block f evaluates pod f (pods[f]) on the nL row versions vidx[f * nL ..] of the slab (host-derived
+// rows of the batch's landed nodes as they were at the pod's turn) into out[f * nL ..]. Reads the slab only.
+hipError_t launch_top_scores_landed(const MirrorView& slab, const PodVec* pods, const Profile& pf, const uint16_t* vidx,
+                                    int nF, int nL, TopLanded* out, hipStream_t st);
+// Loads the two kernels' code (a kernel's first launch otherwise does, on the host's time between two batches).
+hipError_t preload_top_scores();
+
 int64_t host_tiebreak_position(uint64_t seed, uint64_t seq, int64_t T);
 // diagnostics (gs_probe.hip): cycles of one pair evaluation as the commit kernel runs it
 hipError_t launch_probe(int mode, const MirrorView& m, const Profile& pf, const PodVec* pods, int npods,

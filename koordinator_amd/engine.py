@@ -11,6 +11,7 @@
   evaluate               RunFilterPlugins + RunScorePlugins per node  (load_aware.go:123-171,269-335)
   schedule               scheduleOne loop incl. selectHost + Reserve  ([upstream] schedule_one.go)
   schedule_diag          ... with the FitError diagnosis of each pod   ([upstream] framework/types.go FitError)
+  schedule_top_scores    ... with each scored pod's --debug-scores table (frameworkext/debug.go:61-109)
 
 The product path has no CPU fallback: if libgpuscore or a GPU is missing, construction fails.
 """
@@ -151,9 +152,12 @@ class Engine:
 
     def schedule_wait(self, handle):
         """The placements of a schedule_submit handle; (placements, diag) of a schedule_submit_diag handle;
-        (placements, diag, words, row_of) of a schedule_submit_diag_nodes handle."""
+        (placements, diag, words, row_of) of a schedule_submit_diag_nodes handle; (placements, rows, count) of a
+        schedule_submit_top_scores handle."""
         t, *res = handle
         self._chk(lib().gs_schedule_wait(self._h, t), "gs_schedule_wait")
+        if res and isinstance(res[-1], abi.GsTopScores):   # (the handle kept the struct alive)
+            res.pop()
         if res and isinstance(res[-1], abi.GsStatusMap):   # words: the rows handed out
             m = res.pop()
             res[2] = res[2][:m.rows_used]
@@ -197,6 +201,40 @@ class Engine:
                                                       abi.ptr(diag), C.byref(m), C.byref(t)),
                   "gs_schedule_submit_diag_nodes")
         return (t.value, out, diag, words, row_of, m)
+
+    def _top_scores(self, pods, topn):
+        """The caller-owned buffers of a gs_top_scores."""
+        rows = np.zeros((len(pods), max(1, min(int(topn), abi.GS_MAX_TOP_SCORES))), abi.TOP_SCORE_DTYPE)
+        count = np.zeros(len(pods), np.uint32)
+        return rows, count, abi.GsTopScores(rows=abi.ptr(rows), count=abi.ptr(count), topn=int(topn))
+
+    def schedule_top_scores(self, pods, seq=None, topn=8):
+        """gs_schedule_top_scores: (placements, rows, count). rows[i, :count[i]] (abi.TOP_SCORE_DTYPE) is the
+        --debug-scores table of pod i at its turn: its topn best feasible nodes by (total descending, node ascending)
+        with the unweighted plugin scores; count[i] is 0 for a pod with fewer than two feasible nodes.
+        abi.debug_scores_table renders one. One rank, no node sampling."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        rows, count, t = self._top_scores(pods, topn)
+        self._chk(lib().gs_schedule_top_scores(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out),
+                                               C.byref(t)), "gs_schedule_top_scores")
+        return out, rows, count
+
+    def schedule_submit_top_scores(self, pods, seq=None, topn=8):
+        """gs_schedule_submit_top_scores: a handle for schedule_wait, which then returns what schedule_top_scores does."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        rows, count, ts = self._top_scores(pods, topn)
+        t = C.c_uint64(0)
+        self._chk(lib().gs_schedule_submit_top_scores(self._h, abi.ptr(pods), len(pods), abi.ptr(seq), abi.ptr(out),
+                                                      C.byref(ts), C.byref(t)), "gs_schedule_submit_top_scores")
+        return (t.value, out, rows, count, ts)
 
     def schedule_diag(self, pods, seq=None):
         """gs_schedule_diag: (placements, diag); diag[i] (abi.FIT_DIAGNOSIS_DTYPE) is the FitError diagnosis of a pod
