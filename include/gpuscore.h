@@ -1095,6 +1095,18 @@ int gs_reason_string(uint32_t code, uint32_t scalar_mask, const char* const* sca
  * s_memtime stamps of its 8 phases at [2n + 8i ..] (cycles: 10n entries). */
 int gs_debug_pair_probe(gs_ctx* ctx, const gs_pod* pods, uint32_t npods, const uint32_t* nodes, const int32_t* pod_of,
                         uint32_t n, int mode, int32_t* scores, uint64_t* cycles);
+/* Diagnostics: the per-node view of one extension pod. Runs exactly the launches gs_schedule_ext runs for the pod
+ * (eval, ext_nodes, ext_numa, ext_matched, select, finish) and returns what they left for every node, with the select
+ * result; no Reserve and no assume: mirror, devices, reservations, NUMA allocations and the recorded Reserves stay as
+ * they are. rows: 5 rows of num_nodes int32 (GS_EXT_ROW_*): feasible; base, the weighted total of the node plugins (-1
+ * infeasible); the raw DeviceShare score; the nominated reservation's raw score (without PreScore's preferred-node
+ * substitution); total, the normalized weighted sum selectHost compares (-1 infeasible). nominated_uid: num_nodes, 0 =
+ * none. result: GS_EXT_ROWS_RESULT_WORDS words (GS_EXT_ROWS_*); fail_code: a PreFilter failure (GS_EXT_FAIL_POD). */
+enum { GS_EXT_ROW_FEASIBLE = 0, GS_EXT_ROW_BASE, GS_EXT_ROW_DS_RAW, GS_EXT_ROW_RS_RAW, GS_EXT_ROW_TOTAL, GS_EXT_ROWS };
+enum { GS_EXT_ROWS_NODE = 0, GS_EXT_ROWS_SCORE, GS_EXT_ROWS_TIES, GS_EXT_ROWS_FEASIBLE, GS_EXT_ROWS_PREF_NODE,
+       GS_EXT_ROWS_DS_NORM, GS_EXT_ROWS_RS_NORM, GS_EXT_ROWS_FAIL_CODE, GS_EXT_ROWS_RESULT_WORDS };
+int gs_debug_ext_rows(gs_ctx* ctx, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
+                      uint64_t* nominated_uid, int64_t* result);
 /* Diagnostics: the device's topology-manager Merge + admit (frameworkext/topologymanager/policy.go:68-186 and
  * policy_{best_effort,restricted,single_numa_node}.go, as every NUMA-policy pair evaluation runs it) on given hint
  * lists, one gs_merge_case each. The lists are those NodeNUMAResource's hint provider produces

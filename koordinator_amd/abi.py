@@ -348,6 +348,19 @@ GS_POD_EVENT_ADD, GS_POD_EVENT_UPDATE, GS_POD_EVENT_DELETE = 0, 1, 2
 GS_EXT_FAIL_DEVICE, GS_EXT_FAIL_RESERVATION, GS_EXT_FAIL_POD = 0x1000, 0x2000, 0x4000
 
 
+EXT_ROW_KEYS = ("feasible", "base", "ds_raw", "rs_raw", "total")          # GS_EXT_ROW_*
+EXT_ROWS_RESULT_KEYS = ("node", "score", "ties", "feasible_count", "pref_node", "ds_norm", "rs_norm",
+                        "fail_code")                                       # GS_EXT_ROWS_*
+
+
+def ext_rows_dict(rows, nom, res) -> dict:
+    """The (rows[5][N], nominated_uid[N], result[8]) triple of gs_debug_ext_rows as a dict of arrays and ints."""
+    out = {k: rows[i] for i, k in enumerate(EXT_ROW_KEYS)}
+    out["nominated_uid"] = nom
+    out.update({k: int(res[i]) for i, k in enumerate(EXT_ROWS_RESULT_KEYS)})
+    return out
+
+
 class GsGpuDevice(C.Structure):
     _fields_ = [("minor", i32), ("has_info", i32), ("numa_node", i32), ("pad", i32), ("total", i64 * GS_NUM_GPU_RES),
                 ("used", i64 * GS_NUM_GPU_RES)]
@@ -540,6 +553,7 @@ SIGNATURES = {
     "gs_debug_verify_cpuset": (C.c_int, [P, C.c_int]),
     "gs_debug_pair_probe": (C.c_int, [P, P, C.c_uint32, P, P, C.c_uint32, C.c_int, P, P]),
     "gs_debug_numa_merge": (C.c_int, [P, P, u32, P]),
+    "gs_debug_ext_rows": (C.c_int, [P, P, P, u64, P, P, P]),
     "gs_gang_args_default": (None, [C.POINTER(GsGangArgs)]),
     "gs_gang_mgr_create": (C.c_int, [C.POINTER(GsGangArgs), C.POINTER(P)]),
     "gs_gang_mgr_destroy": (C.c_int, [P]),

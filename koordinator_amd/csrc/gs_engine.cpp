@@ -2122,12 +2122,25 @@ int ext_device_reserve(gs_ctx* c, uint32_t node, const int64_t preq[3], uint32_t
   return GS_OK;
 }
 
-// scheduleOne of one extension pod: eval pass (B = 1) -> ext_nodes -> ext_matched -> ext_select, then the Reserve
-// of NodeNUMAResource (no-op on the supported nodes), DeviceShare and Reservation, and assume.
-int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, gs_placement* out,
-                     gs_ext_placement* eo) {
-  *out = gs_placement{-1, 0, 0, 0, 0};
-  *eo = gs_ext_placement{};
+// What the device chain of one extension pod (ext_chain) leaves behind: for the pod's Reserve (ext_schedule_one) and
+// for its per-node view (gs_debug_ext_rows). The result itself is in c->h_xout / c->h_xnom, the matched records in
+// c->xrec / c->xres_uid.
+struct ExtChain {
+  bool early = false;       // PreFilter ended the pod before any launch (fail_code: DeviceShare's, 0: Reservation's)
+  uint32_t fail_code = 0;
+  bool rs_on = false;
+  int64_t greq[3] = {0, 0, 0};
+  uint32_t gmask = 0, gpu_names_all = 0, xres_all = 0;
+  PodVec v{};
+  int nrec = 0;
+  Slot* sl = nullptr;
+  bool ext_ev = false;
+  std::chrono::steady_clock::time_point t0, t_done;
+};
+
+// scheduleOne of one extension pod up to selectHost: eval pass (B = 1) -> ext_nodes -> ext_numa -> ext_matched ->
+// ext_select -> ext_finish, and the wait for the stream. No host or device state of the cluster changes here.
+int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, ExtChain* ch) {
   // several ranks: with the score-row exchange every rank holds every node's state and runs the one-GPU pipeline, so an
   // extension pod runs whole on every rank (no exchange: the same inputs give the same placement everywhere); the
   // level exchange's ranks hold their shard's rows only
@@ -2135,11 +2148,12 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     return fail(c, GS_EUNSUPPORTED, "Reservation / DeviceShare pods need one rank (or the score-row exchange) and no "
                 "node sampling");
   const bool ds_on = c->ext.enabled & GS_EXT_DEVICESHARE, rs_on = c->ext.enabled & GS_EXT_RESERVATION;
-  int64_t greq[3];
-  uint32_t gmask = 0;
+  int64_t* const greq = ch->greq;
+  uint32_t& gmask = ch->gmask;
+  ch->rs_on = rs_on;
   if (ds_on && gpu_request_of(e, greq, &gmask) < 0) {   // DeviceShare PreFilter: UnschedulableAndUnresolvable
-    eo->fail_code = GS_EXT_FAIL_POD;
-    c->stats.pods += 1;
+    ch->early = true;
+    ch->fail_code = GS_EXT_FAIL_POD;
     return GS_OK;
   }
   if (!ds_on) { greq[0] = greq[1] = greq[2] = 0; gmask = 0; }
@@ -2148,9 +2162,10 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
   for (int x = 0; x < GS_MAX_XRES; ++x)
     if (e.xres_requests[x] < 0 || !in_range(e.xres_requests[x]))
       return fail(c, GS_EUNSUPPORTED, "extended resource request outside [0, 2^53)");
-  PodVec v = prep_pod(c, pod);
+  PodVec& v = ch->v;
+  v = prep_pod(c, pod);
   if (rs_on && e.reservation_required && matched.empty()) {   // PreFilter: ErrReasonReservationAffinity
-    c->stats.pods += 1;
+    ch->early = true;
     return GS_OK;
   }
   int rc;
@@ -2225,17 +2240,21 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     c->xrec.push_back(rec);
     a = b;
   }
-  const int nrec = (int)c->xrec.size();
+  const int nrec = ch->nrec = (int)c->xrec.size();
   if ((rc = ext_stage_reserve(c, (uint32_t)nrec, (uint32_t)c->xres.size()))) return rc;
   ExtPod& xp = *c->h_xpod;
   xp = ExtPod{};
   for (int r = 0; r < 3; ++r) { xp.gpu_req[r] = greq[r]; xp.dev_w[r] = c->ext.device_weights[r]; }
   xp.gpu_mask = gmask;
-  const uint32_t gpu_names_all = gmask ? (e.gpu_request_mask & 0x1Fu) : 0u;   // NodeInfo.AddPod adds them all
-  xp.gpu_names = gpu_names_all & ~c->ext.fit_ignored_gpu_names;               // Fit checks the non-ignored ones
+  // NodeInfo.AddPod adds them all
+  const uint32_t gpu_names_all = ch->gpu_names_all = gmask ? (e.gpu_request_mask & 0x1Fu) : 0u;
+  // Fit checks the non-ignored ones ([upstream] fit.go fitsRequest), and only as NodeResourcesFit's Filter: none
+  // with that Filter off
+  const bool fit_filter = c->cfg.enabled & GS_ENABLE_FIT_FILTER;
+  xp.gpu_names = fit_filter ? gpu_names_all & ~c->ext.fit_ignored_gpu_names : 0u;
   for (int n = 0; n < GS_NUM_GPU_NAMES; ++n) xp.gpu_name_req[n] = (xp.gpu_names >> n & 1u) ? e.gpu_requests[n] : 0;
-  const uint32_t xres_all = e.xres_request_mask & ((1u << GS_MAX_XRES) - 1u);
-  const uint32_t xres_fit = xres_all & ~c->ext.fit_ignored_xres;
+  const uint32_t xres_all = ch->xres_all = e.xres_request_mask & ((1u << GS_MAX_XRES) - 1u);
+  const uint32_t xres_fit = fit_filter ? xres_all & ~c->ext.fit_ignored_xres : 0u;
   xp.gpu_names |= xres_fit << GS_NUM_GPU_NAMES;
   for (int x = 0; x < GS_MAX_XRES; ++x)
     xp.gpu_name_req[GS_NUM_GPU_NAMES + x] = (xres_fit >> x & 1u) ? e.xres_requests[x] : 0;
@@ -2316,11 +2335,39 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
     c->hx_gpu += us(hx3 - ext_t0);
     c->hx_pods += 1;
   }
-  if (ext_ev) {
+  ch->sl = &sl;
+  ch->ext_ev = ext_ev;
+  ch->t0 = ext_t0;
+  ch->t_done = hx3;
+  return GS_OK;
+}
+
+// scheduleOne of one extension pod: the device chain (ext_chain), then the Reserve of NodeNUMAResource (no-op on the
+// supported nodes), DeviceShare and Reservation, and assume.
+int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, gs_placement* out,
+                     gs_ext_placement* eo) {
+  *out = gs_placement{-1, 0, 0, 0, 0};
+  *eo = gs_ext_placement{};
+  ExtChain ch;
+  int rc;
+  if ((rc = ext_chain(c, pod, e, seq, &ch))) return rc;
+  if (ch.early) {
+    eo->fail_code = ch.fail_code;
+    c->stats.pods += 1;
+    return GS_OK;
+  }
+  using hx_clk = std::chrono::steady_clock;
+  const bool rs_on = ch.rs_on;
+  const int64_t* const greq = ch.greq;
+  const uint32_t gmask = ch.gmask, gpu_names_all = ch.gpu_names_all, xres_all = ch.xres_all;
+  const PodVec& v = ch.v;
+  const auto hx3 = ch.t_done;
+  if (ch.ext_ev) {
+    Slot& sl = *ch.sl;
     c->stats.eval_ms += ev_ms(sl.ev[0].get(), sl.ev[1].get());
     c->stats.commit_ms += ev_ms(sl.ev[1].get(), sl.ev[4].get());
   } else {
-    c->stats.commit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ext_t0).count();
+    c->stats.commit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ch.t0).count();
   }
   c->stats.eval_launches += 1;
   c->stats.eval_pairs += c->n1 - c->n0;
@@ -4716,6 +4763,64 @@ int gs_schedule_ext(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, uint32
   rc = flush_rows(c);
   if (!rc) rc = ext_flush_devices(c);
   return rc;
+}
+
+// The per-node view of one extension pod: ext_schedule_one's device chain, then the rows it left in HBM. Nothing is
+// reserved or assumed.
+int gs_debug_ext_rows(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
+                      uint64_t* nominated_uid, int64_t* result) {
+  if (!c || !pod || !ext || !rows || !nominated_uid || !result) return GS_EINVAL;
+  quiesce(c);
+  int rc = ready(c);
+  if (rc) return rc;
+  if ((rc = validate_pod(c, *pod))) return rc;
+  const uint32_t N = c->N;
+  for (uint32_t i = 0; i < N; ++i) {
+    rows[i] = 0;
+    rows[N + i] = -1;
+    rows[2 * N + i] = rows[3 * N + i] = 0;
+    rows[4 * N + i] = -1;
+    nominated_uid[i] = 0;
+  }
+  for (int k = 0; k < GS_EXT_ROWS_RESULT_WORDS; ++k) result[k] = 0;
+  result[GS_EXT_ROWS_NODE] = result[GS_EXT_ROWS_PREF_NODE] = -1;
+  ExtChain ch;
+  if ((rc = ext_chain(c, *pod, *ext, seq, &ch))) return rc;
+  if (ch.early) {
+    result[GS_EXT_ROWS_FAIL_CODE] = ch.fail_code;
+    return GS_OK;
+  }
+  const ExtOut xo = *c->h_xout.get();
+  if (xo.err & 1u)
+    return fail(c, GS_EUNSUPPORTED, "a GPU's NUMA node is not one of its node's NUMA zones (DeviceShare hints)");
+  if (xo.err & 2u)
+    return fail(c, GS_EUNSUPPORTED, "the topology-manager merge of a GPU pod exceeds its permutation bound");
+  const uint32_t len = c->n1 - c->n0;
+  std::vector<int32_t> tot(len), T(len);
+  std::vector<int16_t> ds(len), rs(len);
+  HIP_TRY(c, hipMemcpy(tot.data(), c->d_xtot.get(), 4 * (size_t)len, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(T.data(), c->d_xT.get(), 4 * (size_t)len, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(ds.data(), c->d_xds.get(), 2 * (size_t)len, hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(rs.data(), c->d_xrs.get(), 2 * (size_t)len, hipMemcpyDeviceToHost));
+  for (uint32_t j = 0; j < len; ++j) {
+    const uint32_t i = c->n0 + j;
+    rows[i] = tot[j] >= 0 ? 1 : 0;
+    rows[N + i] = tot[j] >= 0 ? tot[j] : -1;
+    rows[2 * N + i] = ds[j];
+    rows[3 * N + i] = rs[j];
+    rows[4 * N + i] = T[j];
+  }
+  const int32_t* h_xnom = c->h_xnom.get();
+  for (int k = 0; k < ch.nrec; ++k)
+    if (ch.rs_on && h_xnom[k] >= 0) nominated_uid[c->xrec[k].node] = c->xres_uid[c->xrec[k].first + h_xnom[k]];
+  result[GS_EXT_ROWS_NODE] = xo.node;
+  result[GS_EXT_ROWS_SCORE] = xo.node >= 0 ? xo.score : 0;
+  result[GS_EXT_ROWS_TIES] = xo.node >= 0 ? xo.ties : 0;
+  result[GS_EXT_ROWS_FEASIBLE] = xo.feasible;
+  result[GS_EXT_ROWS_PREF_NODE] = xo.pref_node;
+  result[GS_EXT_ROWS_DS_NORM] = xo.node >= 0 ? xo.ds_norm : 0;
+  result[GS_EXT_ROWS_RS_NORM] = xo.node >= 0 ? xo.rs_norm : 0;
+  return GS_OK;
 }
 
 }  // extern "C"

@@ -512,6 +512,19 @@ class Engine:
         self.last_probe_stamps = cycles[2 * n:].reshape(n, 8).astype(np.int64)
         return (scores.reshape(n, 64) if mode == 1 else scores), cycles[:n], cycles[n:2 * n]
 
+    def ext_rows(self, pod, ext, seq: int = 0) -> dict:
+        """Diagnostics: the per-node view of one extension pod and its select result (gs_debug_ext_rows); nothing is
+        reserved or assumed. Keys: abi.EXT_ROW_KEYS (arrays over the nodes), nominated_uid, abi.EXT_ROWS_RESULT_KEYS."""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        ext = np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        n = self.cfg.num_nodes
+        rows = np.zeros((len(abi.EXT_ROW_KEYS), n), np.int32)
+        nom = np.zeros(n, np.uint64)
+        res = np.zeros(len(abi.EXT_ROWS_RESULT_KEYS), np.int64)
+        self._chk(lib().gs_debug_ext_rows(self._h, abi.ptr(pod), abi.ptr(ext), int(seq), abi.ptr(rows), abi.ptr(nom),
+                                          abi.ptr(res)), "gs_debug_ext_rows")
+        return abi.ext_rows_dict(rows, nom, res)
+
     def verify_cpusets(self, on: bool = True):
         """Re-run the host takeCPUs for every cpuset the commit kernel selects (schedule fails on a difference)."""
         self._chk(lib().gs_debug_verify_cpuset(self._h, int(on)), "gs_debug_verify_cpuset")

@@ -1769,9 +1769,20 @@ int64_t or_device_score_node(const gs_ext_args* a, const int64_t* total, const i
   return ds_scorer(*a, total, free, q);
 }
 
-// scheduleOne with the extension plugins (one pod at a time, every node checked, no replay).
-int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
-                    gs_placement* out, gs_ext_placement* ext_out) {
+// The per-node view of one extension pod (or_ext_rows): what scheduleOne holds just before selectHost, and the
+// select result. rows: 5 rows of N (feasible, base, ds_raw, rs_raw, total); nom: N uids; res: EXT_ROWS_RES words.
+struct ExtRowsOut {
+  int32_t* rows;
+  uint64_t* nom;
+  int64_t* res;
+};
+enum { XR_NODE = 0, XR_SCORE, XR_TIES, XR_FEASIBLE, XR_PREF, XR_DS_NORM, XR_RS_NORM, XR_FAIL, EXT_ROWS_RES };
+
+// scheduleOne with the extension plugins (one pod at a time, every node checked, no replay). view: the per-node values
+// and the select result of the (single) pod are written there and the pod is not reserved or assumed.
+static int schedule_ext_impl(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods,
+                             const uint64_t* seq, gs_placement* out, gs_ext_placement* ext_out,
+                             const ExtRowsOut* view) {
   if (!c || !out || (npods && !pods)) return GS_EINVAL;
   if (c->cfg.sample_nodes) return GS_EUNSUPPORTED;
   const int N = (int)c->nodes.size();
@@ -1787,6 +1798,17 @@ int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, ui
   // reservations by node, uid order
   std::vector<std::vector<gs_reservation*>> by_node(N);
   for (auto& kv : c->reservations) by_node[kv.second.node].push_back(&kv.second);
+  if (view) {
+    for (int n = 0; n < N; ++n) {
+      view->rows[n] = 0;
+      view->rows[N + n] = -1;
+      view->rows[2 * N + n] = view->rows[3 * N + n] = 0;
+      view->rows[4 * N + n] = -1;
+      view->nom[n] = 0;
+    }
+    for (int k = 0; k < EXT_ROWS_RES; ++k) view->res[k] = 0;
+    view->res[XR_NODE] = view->res[XR_PREF] = -1;
+  }
   for (uint32_t p = 0; p < npods; ++p) {
     const gs_pod& pod = pods[p];
     gs_pod_ext e{};
@@ -1798,6 +1820,7 @@ int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, ui
     if (ds_on && gpu_pod_request(e, &gpu) < 0) {   // DeviceShare PreFilter: UnschedulableAndUnresolvable
       eo.fail_code = GS_EXT_FAIL_POD;
       if (ext_out) ext_out[p] = eo;
+      if (view) view->res[XR_FAIL] = GS_EXT_FAIL_POD;
       continue;
     }
     if (!ds_on) gpu = GpuReq{};
@@ -1925,6 +1948,14 @@ int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, ui
         else if (nominated[n]) rs = score_reservation(pod, *nominated[n], rsv_allocated(*nominated[n]));
       }
       rsl[i] = rs;
+      if (view) {
+        view->rows[n] = 1;
+        view->rows[N + n] = (int32_t)base[n];
+        view->rows[2 * N + n] = (int32_t)dsl[i];
+        view->rows[3 * N + n] =
+            (rs_on && nominated[n]) ? (int32_t)score_reservation(pod, *nominated[n], rsv_allocated(*nominated[n])) : 0;
+        view->nom[n] = (rs_on && nominated[n]) ? nominated[n]->uid : 0;
+      }
     }
     if (ds_on) default_normalize(kMaxNodeScore, false, dsl);
     if (rs_on) default_normalize(kMaxNodeScore, false, rsl);
@@ -1944,6 +1975,18 @@ int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, ui
     o.node = selected; o.score = mx; o.ties = (uint32_t)cnt;
     eo.deviceshare_score = (int32_t)dsl[si];
     eo.reservation_score = (int32_t)rsl[si];
+    if (view) {   // the view stops before Reserve
+      for (int i = 0; i < F; ++i) view->rows[4 * N + fl[i]] = (int32_t)total[i];
+      view->res[XR_NODE] = selected;
+      view->res[XR_SCORE] = mx;
+      view->res[XR_TIES] = cnt;
+      view->res[XR_FEASIBLE] = F;
+      view->res[XR_PREF] = preferred;
+      view->res[XR_DS_NORM] = ds_on ? dsl[si] : 0;
+      view->res[XR_RS_NORM] = rs_on ? rsl[si] : 0;
+      if (ext_out) ext_out[p] = eo;
+      continue;
+    }
     // Reserve: NodeNUMAResource, DeviceShare, Reservation; then assume
     if (en & (GS_ENABLE_NUMA_FILTER | GS_ENABLE_NUMA_SCORE)) {
       orn::PodAllocation pa;
@@ -1978,6 +2021,21 @@ int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, ui
     if (ext_out) ext_out[p] = eo;
   }
   return GS_OK;
+}
+
+int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
+                    gs_placement* out, gs_ext_placement* ext_out) {
+  return schedule_ext_impl(c, pods, ext, npods, seq, out, ext_out, nullptr);
+}
+
+// The per-node view of one extension pod and its select result, without Reserve or assume (mirrors gs_debug_ext_rows).
+int or_ext_rows(or_cluster* c, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
+                uint64_t* nominated_uid, int64_t* result) {
+  if (!c || !pod || !rows || !nominated_uid || !result) return GS_EINVAL;
+  gs_placement pl;
+  gs_ext_placement eo;
+  const ExtRowsOut view{rows, nominated_uid, result};
+  return schedule_ext_impl(c, pod, ext, 1, &seq, &pl, &eo, &view);
 }
 
 }  // extern "C"

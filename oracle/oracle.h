@@ -93,6 +93,10 @@ int or_reservations_remove(or_cluster* c, const uint64_t* uids, uint32_t n);
 int or_reservation_get(or_cluster* c, uint64_t uid, gs_reservation* out);
 int or_schedule_ext(or_cluster* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
                     gs_placement* out, gs_ext_placement* ext_out);
+/* The per-node view of one extension pod just before selectHost, and the select result; no Reserve, no assume (mirrors
+ * gs_debug_ext_rows: the same rows[5][N], nominated_uid[N] and result[GS_EXT_ROWS_RESULT_WORDS] layout). */
+int or_ext_rows(or_cluster* c, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
+                uint64_t* nominated_uid, int64_t* result);
 /* plugin-level restatements for the reference's unit vectors */
 int64_t or_score_reservation(const gs_pod* pod, const gs_reservation* r);   /* scoreReservation (scoring.go:183-203) */
 int or_default_normalize_score(int64_t max_priority, int reverse, int64_t* scores, uint32_t n);

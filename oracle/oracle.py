@@ -72,6 +72,7 @@ def _load() -> C.CDLL:
         "or_reservations_remove": (C.c_int, [P, P, C.c_uint32]),
         "or_reservation_get": (C.c_int, [P, C.c_uint64, P]),
         "or_schedule_ext": (C.c_int, [P, P, P, C.c_uint32, P, P, P]),
+        "or_ext_rows": (C.c_int, [P, P, P, C.c_uint64, P, P, P]),
         "or_score_reservation": (C.c_int64, [P, P]),
         "or_default_normalize_score": (C.c_int, [C.c_int64, C.c_int, P, C.c_uint32]),
         "or_reservation_node_scores": (C.c_int, [P, P, P, C.c_uint32, P, P, P]),
@@ -316,6 +317,18 @@ class Oracle:
         _chk(lib().or_schedule_ext(self._h, abi.ptr(pods), abi.ptr(ext), len(pods), abi.ptr(seq), abi.ptr(out),
                                    abi.ptr(eo)), "schedule_ext")
         return out, eo
+
+    def ext_rows(self, pod, ext, seq: int = 0) -> dict:
+        """The per-node view of one extension pod just before selectHost and the select result, without Reserve
+        (Engine.ext_rows' keys: abi.EXT_ROW_KEYS, nominated_uid, abi.EXT_ROWS_RESULT_KEYS)."""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        ext = np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        rows = np.zeros((len(abi.EXT_ROW_KEYS), self.n), np.int32)
+        nom = np.zeros(self.n, np.uint64)
+        res = np.zeros(len(abi.EXT_ROWS_RESULT_KEYS), np.int64)
+        _chk(lib().or_ext_rows(self._h, abi.ptr(pod), abi.ptr(ext), int(seq), abi.ptr(rows), abi.ptr(nom),
+                               abi.ptr(res)), "ext_rows")
+        return abi.ext_rows_dict(rows, nom, res)
 
     def schedule_replay(self, pods, given, seq=None, nthreads: int = 1):
         """Pods with given[i] >= 0 are placed on that node (Filter there for the affinity, Reserve, assume);
