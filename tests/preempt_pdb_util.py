@@ -154,10 +154,7 @@ def dry_run(o, nodes: np.ndarray, table: Table, pre, rows, lists: dict, budgets:
     def move(i, r, sign, used):
         work["requested"][i] += sign * r["requests"]
         work["pod_count"][i] += sign
-        if not skip and int(r["flags"]) & abi.GS_RESIDENT_QUOTA_TRACKED:
-            for d in range(abi.GS_QUOTA_DIMS):
-                used[d] = max(0, used[d] + sign * int(r["quota_request"][d])) if sign < 0 else \
-                    used[d] + int(r["quota_request"][d])
+        pu.move_used(r, sign, used, skip)
 
     # the potential victims leave; filterPodsWithPDBViolation over them, before any reprieve
     state = {}

@@ -20,6 +20,8 @@ from tests import fit_diag_util as fd
 NOT_POTENTIAL, CANDIDATE, NO_VICTIMS, UNFIT, FITS, ERROR = range(6)
 PRIO = 1000          # the preemptors' priority; residents lie in a band around it
 QUOTA = 1            # the preemptors' quota id
+FIT_BITS = (abi.GS_FAIL_FIT_PODS, abi.GS_FAIL_FIT_CPU, abi.GS_FAIL_FIT_MEMORY, abi.GS_FAIL_FIT_EPHEMERAL,
+            abi.GS_FAIL_FIT_SCALAR)
 
 
 # ---- the pick (pickOneNodeForPreemption with no PDB violations), criterion by criterion ----
@@ -150,6 +152,7 @@ class Answer:
     non_prefix: int                  # candidates with a victim more important than a reprieved potential victim
     quota_victims_on_fitting: int    # victims on nodes the pod fits with nobody evicted
     amp_flips: int = 0               # nodes whose Filter fails at some step on the amplified-CPU check alone
+    only_bits: int = 0               # the Fit bits that were the only failing bit of some reprieve step's Filter code
 
 
 def exceeds(pre, used) -> bool:
@@ -158,6 +161,19 @@ def exceeds(pre, used) -> bool:
     m = int(pre["quota_request_mask"]) & int(pre["limit_mask"])
     return any((m >> d & 1) and used[d] + int(pre["quota_request"][d]) > int(pre["used_limit"][d])
                for d in range(abi.GS_QUOTA_DIMS))
+
+
+def move_used(r, sign: int, used, skip: bool) -> None:
+    """The plugin's AddPod (+1) / RemovePod (-1) on `used`: the request of a tracked resident over its own keys
+    (quota_request_mask; a value outside the mask is no key of the request and moves nothing), floored at zero per
+    dimension when it leaves."""
+    if skip or not int(r["flags"]) & abi.GS_RESIDENT_QUOTA_TRACKED:
+        return
+    for d in range(abi.GS_QUOTA_DIMS):
+        if not int(r["quota_request_mask"]) >> d & 1:
+            continue
+        q = int(r["quota_request"][d])
+        used[d] = max(0, used[d] - q) if sign < 0 else used[d] + q
 
 
 def dry_run(o: orc.Oracle, nodes: np.ndarray, table: Table, pre, rows=None) -> Answer:
@@ -196,10 +212,7 @@ def dry_run(o: orc.Oracle, nodes: np.ndarray, table: Table, pre, rows=None) -> A
         """NodeInfo.AddPodInfo (+1) / RemovePod (-1) of resident r on node i, and the plugin's AddPod / RemovePod"""
         work["requested"][i] += sign * r["requests"]
         work["pod_count"][i] += sign
-        if not skip and int(r["flags"]) & abi.GS_RESIDENT_QUOTA_TRACKED:
-            for d in range(abi.GS_QUOTA_DIMS):
-                used[d] = max(0, used[d] + sign * int(r["quota_request"][d])) if sign < 0 else \
-                    used[d] + int(r["quota_request"][d])
+        move_used(r, sign, used, skip)
 
     # 3a. the potential victims leave
     state = {}
@@ -222,6 +235,7 @@ def dry_run(o: orc.Oracle, nodes: np.ndarray, table: Table, pre, rows=None) -> A
             del state[i]
     # 3d. reprieve, one potential victim per node and step
     amp_nodes = set()
+    only_bits = 0
     step = 0
     while True:
         cur = [i for i, s in state.items() if not s["err"] and step < len(s["pv"])]
@@ -240,6 +254,8 @@ def dry_run(o: orc.Oracle, nodes: np.ndarray, table: Table, pre, rows=None) -> A
                 if (int(codes[i]) & abi.GS_FAIL_NUMA_MASK) >> abi.GS_FAIL_NUMA_SHIFT == abi.GS_NUMA_INSUFFICIENT_AMP_CPU \
                         and not int(codes[i]) & 0x3F:
                     amp_nodes.add(i)
+                if int(codes[i]) in FIT_BITS:
+                    only_bits |= int(codes[i])
                 move(i, r, -1, s["used"])
                 removed = True
                 s["victims"].append(j)
@@ -275,7 +291,7 @@ def dry_run(o: orc.Oracle, nodes: np.ndarray, table: Table, pre, rows=None) -> A
             qv += len(v)
     k, crit = pick(cands)
     ans = Answer(abi.GS_PREEMPT_NO_CANDIDATES, -1, [], len(potential), len(cands), nerr, status, bits, cands, crit,
-                 non_prefix, qv, len(amp_nodes))
+                 non_prefix, qv, len(amp_nodes), only_bits)
     if not potential:
         ans.status = abi.GS_PREEMPT_NO_POTENTIAL_NODES
     elif k >= 0:

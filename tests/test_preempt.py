@@ -6,10 +6,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from koordinator_amd import abi, build, synth
-from oracle import oracle as orc
+from koordinator_amd import abi, build
 from tests import fit_diag_util as fd
 from tests import preempt_util as pu
+from tests.preempt_edges_util import CPU, one_node, pod_of, resident
 
 
 @pytest.fixture(scope="module")
@@ -95,46 +95,7 @@ def test_struct_sizes(lib):
     assert abi.STRUCT_SIZES["gs_preempt_candidate"] == 32 and abi.GS_ABI_VERSION == 6
 
 
-# ---- the restatement on a one-node cluster ----
-CPU, GI = 1000, 1 << 30
-
-
-def one_node(free_cpu: int):
-    """A 16-CPU node with free_cpu milli-CPU left (memory never binds, no NodeMetric: LoadAware passes), the oracle in
-    that state, and a pod builder."""
-    c = synth.make_cluster(1, 1, 0)
-    n = c.nodes[0]
-    n["allocatable"][:3] = (16 * CPU, 64 * GI, 500 * GI)
-    n["requested"][:] = 0
-    n["requested"][0] = 16 * CPU - free_cpu
-    n["nonzero_requested"][:] = (n["requested"][0], 0)
-    n["pod_count"], n["allowed_pod_number"] = 10, 110
-    n["raw_allocatable_mask"] = n["custom_flags"] = 0
-    c.metrics["exists"] = 0
-    c.assigned_pods = c.assigned_pods[:0]
-    o = orc.Oracle(fd.make_cfg(c, False))
-    synth.load_into(o, c)
-    return c, o
-
-
-def pod_of(c, cpu: int):
-    p = c.pods[0].copy()
-    p["requests"][:] = 0
-    p["requests"][0] = p["nonzero_requests"][0] = cpu
-    p["requests"][1] = p["nonzero_requests"][1] = GI
-    p["limits"][:] = p["requests"]
-    p["request_mask"] = 3
-    return p
-
-
-def resident(uid, cpu, prio, start=0, quota=pu.QUOTA, flags=abi.GS_RESIDENT_QUOTA_TRACKED):
-    r = np.zeros(1, abi.RESIDENT_POD_DTYPE)[0]
-    r["uid"], r["start_time_ns"], r["priority"], r["quota"], r["flags"] = uid, start, prio, quota, flags
-    r["requests"][0] = r["quota_request"][0] = cpu
-    r["quota_request_mask"] = 1
-    return r
-
-
+# ---- the restatement on a one-node cluster (the builders: tests/preempt_edges_util.py) ----
 def run(free_cpu, residents, cpu, used, limit, **kw):
     c, o = one_node(free_cpu)
     t = pu.Table(1)
