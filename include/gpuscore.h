@@ -595,7 +595,8 @@ void gs_numa_args_default(gs_numa_args* a);
 /* ---- Reservation + DeviceShare ----
  * The two plugins of the shipped profile that normalize their scores (config/manager/scheduler-config.yaml:80-89:
  * DeviceShare weight 1, Reservation weight 5000). Scope on the device path: GPU devices (the GPU device type of
- * deviceshare/utils.go:47-56; no RDMA / FPGA, no joint allocation, no VF or PCIe hints, no device hint selectors);
+ * deviceshare/utils.go:47-56) through gs_schedule_ext, and the RDMA and FPGA types (devicehandler_default.go:32-35)
+ * through gs_schedule_ext_aux below; no joint allocation, no VF or PCIe hints, no device hint selectors);
  * reservations holding cpu / memory / ephemeral / the scalar slots (no cpuset or device reservations, no host
  * ports, no preemption nomination). A pod uses the extension path when it requests GPUs or matches a reservation
  * (or requires one); it is then scheduled alone, through the normalizing select kernel. Every other pod keeps the
@@ -728,6 +729,56 @@ int gs_schedule_ext(gs_ctx* ctx, const gs_pod* pods, const gs_pod_ext* ext, uint
  * reservation_uid / gpu_minor_mask / gpu_count / gpu_per_instance of *out are filled, the rest of *out is 0;
  * 0 = none (never placed by gs_schedule_ext, or forgotten / unassigned since). */
 int gs_ext_reserved_get(gs_ctx* ctx, uint64_t uid, uint32_t* node, gs_ext_placement* out);
+
+/* ---- DeviceShare device types beyond GPU: RDMA and FPGA (DefaultDeviceHandler, devicehandler_default.go:32-93) ----
+ * Each type has one resource name ("koordinator.sh/rdma", "koordinator.sh/fpga"); q = the pod's request of it (0: none;
+ * q > 100 with q % 100 != 0 fails PreFilter like an invalid GPU request, utils.go:84-90,147-175). The per-node Filter
+ * (Prepare, filterNodeDevice, defaultAllocateDevices) and raw Score (scoreNode per requested type, summed with the GPU
+ * type's: up to 300) run in ext_nodes_kernel, Reserve / Unreserve of the minors on the host. Fit of the two names: the
+ * caller registers them as two of its GS_MAX_XRES extended resources (gs_pod_ext.xres_requests, gs_node_devices.xres_*).
+ * Refused with GS_EUNSUPPORTED for a pod requesting one of the types: any node with a NUMA topology policy (DeviceShare as
+ * hint provider for several types, topology_hint.go:108-214, is not restated), a reservation owner or a required
+ * reservation. Not modelled: hint / VF selectors, virtual functions, the PCIe-level exclusive policy, joint allocation,
+ * device reservations. Several ranks: the rule of gs_schedule_ext (untested for these types). */
+enum gs_aux_device_type { GS_AUX_RDMA = 0, GS_AUX_FPGA = 1, GS_NUM_AUX_TYPES = 2 };
+#define GS_MAX_AUX_DEVICES 8       /* per type and node; minors 0..31, distinct per type */
+enum gs_aux_strategy {             /* DeviceHint.AllocateStrategy of the type (apis/extension/device_share.go) */
+  GS_AUX_STRATEGY_NONE = 0, GS_AUX_APPLY_FOR_ALL = 1, GS_AUX_REQUESTS_AS_COUNT = 2
+};
+typedef struct gs_aux_device {     /* one minor of deviceTotal[type] / deviceUsed[type] */
+  int32_t minor;
+  int32_t has_info;                /* a DeviceInfo exists for the minor (only those are candidates) */
+  int32_t numa_node;               /* DeviceInfo.Topology.NodeID, -1: none (validated, not read yet: multi-type hints) */
+  int32_t pad;
+  int64_t total;                   /* 0: an unhealthy device (it still counts in len(deviceTotal[type])) */
+  int64_t used;
+} gs_aux_device;
+typedef struct gs_node_aux_devices {
+  int32_t num[GS_NUM_AUX_TYPES];
+  gs_aux_device dev[GS_NUM_AUX_TYPES][GS_MAX_AUX_DEVICES];
+} gs_node_aux_devices;
+typedef struct gs_pod_aux {
+  int64_t request[GS_NUM_AUX_TYPES];           /* q per type */
+  int32_t strategy[GS_NUM_AUX_TYPES];          /* gs_aux_strategy (ignored when q > 100) */
+  int32_t device_exclusive[GS_NUM_AUX_TYPES];  /* DeviceHint.ExclusivePolicy == DeviceLevel */
+} gs_pod_aux;
+typedef struct gs_aux_placement {
+  uint32_t minor_mask[GS_NUM_AUX_TYPES];       /* minors the Reserve allocated (bit = minor) */
+  int32_t count[GS_NUM_AUX_TYPES];
+  int64_t per_instance[GS_NUM_AUX_TYPES];      /* the DeviceAllocation.Resources of each minor */
+} gs_aux_placement;
+/* ScoringStrategy.Resources weights of the two names (default 0: device and node scores of the type are 0) */
+int gs_ext_configure_aux(gs_ctx* ctx, const int64_t weights[GS_NUM_AUX_TYPES]);
+/* Device informer, the RDMA / FPGA entries of the node's Device object (gs_node_devices.has_device says whether the
+ * object exists at all) */
+int gs_node_aux_devices_upsert(gs_ctx* ctx, const uint32_t* idx, const gs_node_aux_devices* dev, uint32_t n);
+int gs_node_aux_devices_get(gs_ctx* ctx, uint32_t node, gs_node_aux_devices* out);
+/* gs_schedule_ext with aux[i] (aux may be NULL: gs_schedule_ext is exactly that call; ext must be given with aux) and
+ * aux_out[i] (may be NULL). A pod requesting one of the types takes the extension path. */
+int gs_schedule_ext_aux(gs_ctx* ctx, const gs_pod* pods, const gs_pod_ext* ext, const gs_pod_aux* aux, uint32_t npods,
+                        const uint64_t* seq, gs_placement* out, gs_ext_placement* ext_out, gs_aux_placement* aux_out);
+/* The RDMA / FPGA part of the recorded Reserve of an assumed pod (gs_ext_reserved_get reports the rest). 1 found, 0 none */
+int gs_ext_aux_reserved_get(gs_ctx* ctx, uint64_t uid, uint32_t* node, gs_aux_placement* out);
 
 /* Multi-GPU: nodes are sharded in contiguous ranges [r*ceil(N/R), (r+1)*ceil(N/R)); every rank keeps the full
  * mirror (replicated deltas) and evaluates only its shard. Per batch the shards' score rows are all-gathered and every
@@ -1107,6 +1158,9 @@ enum { GS_EXT_ROWS_NODE = 0, GS_EXT_ROWS_SCORE, GS_EXT_ROWS_TIES, GS_EXT_ROWS_FE
        GS_EXT_ROWS_DS_NORM, GS_EXT_ROWS_RS_NORM, GS_EXT_ROWS_FAIL_CODE, GS_EXT_ROWS_RESULT_WORDS };
 int gs_debug_ext_rows(gs_ctx* ctx, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
                       uint64_t* nominated_uid, int64_t* result);
+/* ... of a pod with RDMA / FPGA requests (aux may be NULL): the same layout */
+int gs_debug_ext_rows_aux(gs_ctx* ctx, const gs_pod* pod, const gs_pod_ext* ext, const gs_pod_aux* aux, uint64_t seq,
+                          int32_t* rows, uint64_t* nominated_uid, int64_t* result);
 /* Diagnostics: the device's topology-manager Merge + admit (frameworkext/topologymanager/policy.go:68-186 and
  * policy_{best_effort,restricted,single_numa_node}.go, as every NUMA-policy pair evaluation runs it) on given hint
  * lists, one gs_merge_case each. The lists are those NodeNUMAResource's hint provider produces
@@ -1245,7 +1299,8 @@ int gs_gang_pass_carried(gs_gang_pass* p, uint64_t* uids, int8_t* states, uint32
  * gs_node_metric, gs_pod_metric, gs_config, gs_placement, gs_stats, gs_loadaware_args, gs_cpu_topology,
  * gs_node_numa, gs_pod_allocation, gs_numa_args, gs_quota_group, gs_quota_status, gs_node_devices, gs_reservation,
  * gs_pod_ext, gs_ext_args, gs_ext_placement, gs_status_map, gs_resident_pod, gs_preemptor, gs_preempt_result,
- * gs_preempt_detail, gs_preempt_candidate, gs_preempt_result_pdb, gs_preempt_detail_pdb, gs_preempt_candidate_pdb. */
+ * gs_preempt_detail, gs_preempt_candidate, gs_preempt_result_pdb, gs_preempt_detail_pdb, gs_preempt_candidate_pdb,
+ * gs_top_score, gs_top_scores, gs_aux_device, gs_node_aux_devices, gs_pod_aux, gs_aux_placement. */
 void gs_abi_sizes(uint64_t* out, uint32_t n);
 
 #ifdef __cplusplus

@@ -397,6 +397,32 @@ class GsExtPlacement(C.Structure):
                 ("fail_code", u32), ("pad0", u32)]
 
 
+# ---- DeviceShare device types beyond GPU: RDMA and FPGA (gs_schedule_ext_aux) ----
+GS_AUX_RDMA, GS_AUX_FPGA, GS_NUM_AUX_TYPES = 0, 1, 2
+GS_MAX_AUX_DEVICES = 8
+GS_AUX_STRATEGY_NONE, GS_AUX_APPLY_FOR_ALL, GS_AUX_REQUESTS_AS_COUNT = 0, 1, 2
+AUX_NAMES = {"koordinator.sh/rdma": GS_AUX_RDMA, "koordinator.sh/fpga": GS_AUX_FPGA}
+AUX_STRATEGY = {"": 0, "ApplyForAll": 1, "RequestsAsCount": 2}
+
+
+class GsAuxDevice(C.Structure):
+    _fields_ = [("minor", i32), ("has_info", i32), ("numa_node", i32), ("pad", i32), ("total", i64), ("used", i64)]
+
+
+class GsNodeAuxDevices(C.Structure):
+    _fields_ = [("num", i32 * GS_NUM_AUX_TYPES), ("dev", (GsAuxDevice * GS_MAX_AUX_DEVICES) * GS_NUM_AUX_TYPES)]
+
+
+class GsPodAux(C.Structure):
+    _fields_ = [("request", i64 * GS_NUM_AUX_TYPES), ("strategy", i32 * GS_NUM_AUX_TYPES),
+                ("device_exclusive", i32 * GS_NUM_AUX_TYPES)]
+
+
+class GsAuxPlacement(C.Structure):
+    _fields_ = [("minor_mask", u32 * GS_NUM_AUX_TYPES), ("count", i32 * GS_NUM_AUX_TYPES),
+                ("per_instance", i64 * GS_NUM_AUX_TYPES)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 
 # numpy dtypes with the exact C layout (for bulk construction of node/pod arrays)
@@ -482,6 +508,9 @@ NODE_DEVICES_DTYPE = np.dtype(GsNodeDevices)
 RESERVATION_DTYPE = np.dtype(GsReservation)
 POD_EXT_DTYPE = np.dtype(GsPodExt)
 EXT_PLACEMENT_DTYPE = np.dtype(GsExtPlacement)
+NODE_AUX_DEVICES_DTYPE = np.dtype(GsNodeAuxDevices)
+POD_AUX_DTYPE = np.dtype(GsPodAux)
+AUX_PLACEMENT_DTYPE = np.dtype(GsAuxPlacement)
 RESIDENT_POD_DTYPE = np.dtype(GsResidentPod)
 PREEMPTOR_DTYPE = np.dtype(GsPreemptor)
 PREEMPT_RESULT_DTYPE = np.dtype(GsPreemptResult)
@@ -505,6 +534,12 @@ STRUCT_SIZES = {
     "gs_preempt_result_pdb": C.sizeof(GsPreemptResultPdb), "gs_preempt_detail_pdb": C.sizeof(GsPreemptDetailPdb),
     "gs_preempt_candidate_pdb": C.sizeof(GsPreemptCandidatePdb),
     "gs_top_score": C.sizeof(GsTopScore), "gs_top_scores": C.sizeof(GsTopScores),
+}
+# gs_abi_sizes goes on after STRUCT_SIZES with the RDMA / FPGA structs (a table of their own: STRUCT_SIZES keeps its
+# length and last entries)
+AUX_STRUCT_SIZES = {
+    "gs_aux_device": C.sizeof(GsAuxDevice), "gs_node_aux_devices": C.sizeof(GsNodeAuxDevices),
+    "gs_pod_aux": C.sizeof(GsPodAux), "gs_aux_placement": C.sizeof(GsAuxPlacement),
 }
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -616,6 +651,12 @@ SIGNATURES = {
     "gs_reservation_get": (C.c_int, [P, u64, C.POINTER(GsReservation)]),
     "gs_schedule_ext": (C.c_int, [P, P, P, u32, P, P, P]),
     "gs_ext_reserved_get": (C.c_int, [P, u64, P, P]),
+    "gs_ext_configure_aux": (C.c_int, [P, P]),
+    "gs_node_aux_devices_upsert": (C.c_int, [P, P, P, u32]),
+    "gs_node_aux_devices_get": (C.c_int, [P, u32, P]),
+    "gs_schedule_ext_aux": (C.c_int, [P, P, P, P, u32, P, P, P, P]),
+    "gs_ext_aux_reserved_get": (C.c_int, [P, u64, P, P]),
+    "gs_debug_ext_rows_aux": (C.c_int, [P, P, P, P, u64, P, P, P]),
     "gs_node_pods_add": (C.c_int, [P, P, P, u32]),
     "gs_node_pods_remove": (C.c_int, [P, P, P, u32]),
     "gs_node_pods_get": (C.c_int, [P, u32, P, u32]),

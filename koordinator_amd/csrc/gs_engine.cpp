@@ -235,6 +235,7 @@ struct ExtReserved {
   uint32_t gpu_names = 0, xres = 0;             // NodeInfo.AddPod: GPU names / registered extended resources added
   int64_t gpu_name_req[GS_NUM_GPU_NAMES] = {};
   int64_t xres_req[GS_MAX_XRES] = {};
+  gs_aux_placement aux = {};                    // RDMA / FPGA minors and per-instance amounts (ext_aux_reserve)
 };
 
 // Members are destroyed in reverse order: the buffers go first, then the events, then the streams (gs_destroy).
@@ -372,6 +373,15 @@ struct gs_ctx {
   std::map<uint64_t, gs_reservation> rsv;        // reservationCache by uid (uid order = the harness's iteration order)
   std::vector<std::vector<uint64_t>> rsv_node;   // uids per node, ascending
   std::unordered_map<uint64_t, std::vector<uint64_t>> rsv_owner;   // owner key -> uids
+  // RDMA / FPGA devices (gs_node_aux_devices_upsert): empty until the first upsert; the HBM image exists from the first
+  // pod requesting one of the types on (ext_aux_alloc), and only then are rows marked dirty
+  std::vector<gs_node_aux_devices> aux;
+  std::vector<uint8_t> aux_dirty;
+  std::vector<uint32_t> aux_dirty_list;
+  int64_t aux_weights[GS_NUM_AUX_TYPES] = {0, 0};
+  DevBuf<DevAuxNode> d_aux;
+  PinnedBuf<DevAuxNode> h_aux_stage;
+  DevBuf<DevAuxNode> d_aux_stage;
   DevBuf<DevNode> d_dev;
   PinnedBuf<DevNode> h_dev_stage;   // ext_flush_devices staging (pinned / device): images, then node indices
   DevBuf<DevNode> d_dev_stage;
@@ -2032,6 +2042,147 @@ void dev_mark(gs_ctx* c, uint32_t i) {
   if (!c->dev_dirty[i]) { c->dev_dirty[i] = 1; c->dev_dirty_list.push_back(i); }
 }
 
+// ---- RDMA / FPGA devices: the table beside c->devs, its HBM image beside d_dev
+DevAuxNode aux_image(const gs_ctx* c, uint32_t i) {
+  DevAuxNode o{};
+  if (c->aux.empty()) return o;
+  const gs_node_aux_devices& a = c->aux[i];
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T) {
+    o.num[T] = std::min<int32_t>(a.num[T], GS_MAX_AUX_DEVICES);
+    for (int k = 0; k < o.num[T]; ++k) {
+      o.d[T][k].total = a.dev[T][k].total;
+      o.d[T][k].free = std::max<int64_t>(0, a.dev[T][k].total - a.dev[T][k].used);
+      o.d[T][k].minor = a.dev[T][k].minor;
+      o.d[T][k].has_info = a.dev[T][k].has_info ? 1 : 0;
+    }
+  }
+  return o;
+}
+
+void aux_mark(gs_ctx* c, uint32_t i) {
+  if (!c->d_aux) return;   // (ext_aux_alloc uploads every row)
+  if (c->aux_dirty.empty()) c->aux_dirty.assign(c->N, 0);
+  if (!c->aux_dirty[i]) { c->aux_dirty[i] = 1; c->aux_dirty_list.push_back(i); }
+}
+
+int ext_aux_alloc(gs_ctx* c) {
+  if (c->d_aux) return GS_OK;
+  HIP_TRY(c, c->d_aux.alloc(sizeof(DevAuxNode) * std::max<uint32_t>(1, c->N)));
+  std::vector<DevAuxNode> img(c->N);
+  for (uint32_t i = 0; i < c->N; ++i) img[i] = aux_image(c, i);
+  HIP_TRY(c, hipMemcpy(c->d_aux.get(), img.data(), sizeof(DevAuxNode) * c->N, hipMemcpyHostToDevice));
+  c->aux_dirty_list.clear();
+  std::fill(c->aux_dirty.begin(), c->aux_dirty.end(), 0);
+  return GS_OK;
+}
+
+// the dirty nodes' aux images, staged like the Device images (ext_flush_devices)
+int ext_flush_aux(gs_ctx* c) {
+  if (c->aux_dirty_list.empty() || !c->d_aux) return GS_OK;
+  if (!c->h_aux_stage) {
+    HIP_TRY(c, c->h_aux_stage.alloc((sizeof(DevAuxNode) + 4) * EXT_DEV_STAGE));
+    HIP_TRY(c, c->d_aux_stage.alloc((sizeof(DevAuxNode) + 4) * EXT_DEV_STAGE));
+  }
+  DevAuxNode *const h_stage = c->h_aux_stage.get(), *const d_stage = c->d_aux_stage.get();
+  for (size_t done = 0; done < c->aux_dirty_list.size();) {
+    const uint32_t n = (uint32_t)std::min<size_t>(EXT_DEV_STAGE, c->aux_dirty_list.size() - done);
+    HIP_TRY(c, host_wait_stream(c->st.get()));   // the previous scatter has consumed the staging buffers
+    uint32_t* h_idx = reinterpret_cast<uint32_t*>(h_stage + n);
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t i = c->aux_dirty_list[done + j];
+      h_stage[j] = aux_image(c, i);
+      h_idx[j] = i;
+      c->aux_dirty[i] = 0;
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_stage, h_stage, (sizeof(DevAuxNode) + 4) * n, hipMemcpyHostToDevice, c->st.get()));
+    HIP_TRY(c, launch_scatter_auxnodes(c->d_aux.get(), reinterpret_cast<const uint32_t*>(d_stage + n), d_stage, n,
+                                       c->st.get()));
+    done += n;
+  }
+  c->aux_dirty_list.clear();
+  return GS_OK;
+}
+
+// DefaultDeviceHandler.CalcDesiredRequestsAndCount (devicehandler_default.go:44-93) for q > 0 on a node listing n
+// devices of the type
+void aux_desired(int64_t q, int32_t strategy, int32_t exclusive, int n, int64_t* inst, int64_t* count) {
+  *inst = q;
+  *count = 1;
+  if (q > 100 && q % 100 == 0) { *count = q / 100; *inst = 100; }
+  else if (strategy == GS_AUX_APPLY_FOR_ALL) *count = n;
+  else if (strategy == GS_AUX_REQUESTS_AS_COUNT) { *count = q; *inst = exclusive ? 100 : 1; }
+}
+
+// DeviceShare Reserve of one RDMA / FPGA type on one node's row (plugin.go:377-430 -> defaultAllocateDevices,
+// device_allocator.go:397-467): the minors by scoreDevice (scoring.go:186-211) descending, then minor ascending
+// (device_resources.go:171-208); exactly count of them get used += inst. false: fewer than count usable devices
+bool aux_reserve_row(gs_node_aux_devices* a, int T, int64_t q, int32_t strategy, int32_t exclusive, int64_t weight,
+                     bool most, gs_aux_placement* ao) {
+  const int n = a->num[T];
+  if (n <= 0) return false;
+  int64_t inst, count;
+  aux_desired(q, strategy, exclusive, n, &inst, &count);
+  struct Cand { int k; int64_t score; };
+  std::vector<Cand> cs;
+  bool all_zero = true;
+  for (int k = 0; k < n; ++k) all_zero &= a->dev[T][k].total <= a->dev[T][k].used;
+  if (all_zero) return false;
+  for (int k = 0; k < n; ++k) {
+    const gs_aux_device& x = a->dev[T][k];
+    if (!x.has_info) continue;
+    const int64_t t = x.total, f = std::max<int64_t>(0, x.total - x.used);
+    int64_t sc = 0;
+    if (weight && t != 0) {
+      int64_t rq = t;
+      if (t >= f) rq = t - f + inst;
+      sc = most ? (std::min(rq, t) * 100) / t : (rq > t ? 0 : ((t - rq) * 100) / t);
+    }
+    cs.push_back({k, sc});
+  }
+  std::stable_sort(cs.begin(), cs.end(), [&](const Cand& x, const Cand& y) {
+    if (x.score != y.score) return x.score > y.score;
+    return a->dev[T][x.k].minor < a->dev[T][y.k].minor;
+  });
+  std::vector<int> take;
+  for (const Cand& x : cs) {
+    const gs_aux_device& dv = a->dev[T][x.k];
+    const int64_t f = std::max<int64_t>(0, dv.total - dv.used);
+    if (f == 0 || inst > f) continue;
+    take.push_back(x.k);
+    if ((int64_t)take.size() == count) break;
+  }
+  if ((int64_t)take.size() < count) return false;
+  for (int k : take) {
+    a->dev[T][k].used += inst;
+    ao->minor_mask[T] |= 1u << (a->dev[T][k].minor & 31);
+  }
+  ao->count[T] = (int32_t)count;
+  ao->per_instance[T] = inst;
+  return true;
+}
+
+// DeviceShare Unreserve of the recorded RDMA / FPGA minors (updateCacheUsed(..., false), device_cache.go:124-201):
+// SubtractWithNonNegativeResult on the minors the row still has
+void aux_unreserve_row(gs_node_aux_devices* a, const gs_aux_placement& x) {
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T) {
+    if (!x.minor_mask[T]) continue;
+    for (int k = 0; k < a->num[T] && k < GS_MAX_AUX_DEVICES; ++k) {
+      gs_aux_device& dv = a->dev[T][k];
+      if (dv.minor < 0 || dv.minor > 31 || !(x.minor_mask[T] >> dv.minor & 1u)) continue;
+      dv.used = std::max<int64_t>(0, dv.used - x.per_instance[T]);
+    }
+  }
+}
+
+// DeviceShare Unreserve of recorded GPU minors: SubtractWithNonNegativeResult on the minors the Device row still has
+void gpu_unreserve_row(gs_node_devices* d, uint32_t minor_mask, uint32_t keys, const int64_t inst[GS_NUM_GPU_RES]) {
+  for (int g = 0; g < d->num_gpus; ++g) {
+    if (d->gpus[g].minor < 0 || d->gpus[g].minor > 31 || !(minor_mask >> d->gpus[g].minor & 1u)) continue;
+    for (int r = 0; r < GS_NUM_GPU_RES; ++r)
+      if (keys >> r & 1u) d->gpus[g].used[r] = std::max<int64_t>(0, d->gpus[g].used[r] - inst[r]);
+  }
+}
+
 // the pod's matched reservations grouped by node (node order, uid order within a node)
 void matched_of(const gs_ctx* c, uint64_t owner, std::vector<std::pair<uint32_t, uint64_t>>* out) {
   out->clear();
@@ -2045,7 +2196,10 @@ void matched_of(const gs_ctx* c, uint64_t owner, std::vector<std::pair<uint32_t,
   std::sort(out->begin(), out->end());
 }
 
-bool is_ext_pod(const gs_ctx* c, const gs_pod_ext& e) {
+bool is_ext_pod(const gs_ctx* c, const gs_pod_ext& e, const gs_pod_aux* ax = nullptr) {
+  if (ax && (c->ext.enabled & GS_EXT_DEVICESHARE))   // an RDMA / FPGA request
+    for (int T = 0; T < GS_NUM_AUX_TYPES; ++T)
+      if (ax->request[T]) return true;
   if (e.xres_request_mask & ((1u << GS_MAX_XRES) - 1u)) return true;   // Fit over a registered extended resource
   if ((c->ext.enabled & GS_EXT_DEVICESHARE) && (e.gpu_request_mask & 0x1Fu)) return true;
   if (!(c->ext.enabled & GS_EXT_RESERVATION)) return false;
@@ -2131,6 +2285,7 @@ struct ExtChain {
   bool rs_on = false;
   int64_t greq[3] = {0, 0, 0};
   uint32_t gmask = 0, gpu_names_all = 0, xres_all = 0;
+  uint32_t amask = 0;       // RDMA / FPGA types the pod requests
   PodVec v{};
   int nrec = 0;
   Slot* sl = nullptr;
@@ -2140,7 +2295,7 @@ struct ExtChain {
 
 // scheduleOne of one extension pod up to selectHost: eval pass (B = 1) -> ext_nodes -> ext_numa -> ext_matched ->
 // ext_select -> ext_finish, and the wait for the stream. No host or device state of the cluster changes here.
-int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, ExtChain* ch) {
+int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, const gs_pod_aux* ax, uint64_t seq, ExtChain* ch) {
   // several ranks: with the score-row exchange every rank holds every node's state and runs the one-GPU pipeline, so an
   // extension pod runs whole on every rank (no exchange: the same inputs give the same placement everywhere); the
   // level exchange's ranks hold their shard's rows only
@@ -2151,6 +2306,31 @@ int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, E
   int64_t* const greq = ch->greq;
   uint32_t& gmask = ch->gmask;
   ch->rs_on = rs_on;
+  // RDMA / FPGA requests (GetPodDeviceRequests, utils.go:232-252): what is not restated is refused first
+  uint32_t& amask = ch->amask;
+  amask = 0;
+  for (int T = 0; ax && ds_on && T < GS_NUM_AUX_TYPES; ++T) {
+    if (!ax->request[T]) continue;
+    if (ax->request[T] < 0 || ax->request[T] >= (1LL << 53))
+      return fail(c, GS_EUNSUPPORTED, "RDMA / FPGA request outside [0, 2^53)");
+    if (ax->strategy[T] < GS_AUX_STRATEGY_NONE || ax->strategy[T] > GS_AUX_REQUESTS_AS_COUNT)
+      return fail(c, GS_EINVAL, "unknown device allocate strategy %d", ax->strategy[T]);
+    amask |= 1u << T;
+  }
+  if (amask && (e.reservation_owner || e.reservation_required))
+    return fail(c, GS_EUNSUPPORTED, "a pod requesting RDMA / FPGA devices with a reservation owner or a required "
+                "reservation is not supported");
+  if (amask && c->numa_on)
+    for (uint32_t n = 0; n < c->N; ++n)
+      if (c->numa[n].cfg.numa_topology_policy != GS_NUMA_POLICY_NONE)
+        return fail(c, GS_EUNSUPPORTED, "a pod requesting RDMA / FPGA devices while node %u has a NUMA topology policy "
+                    "is not supported (DeviceShare hints for several device types)", n);
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T)   // ValidatePercentageResource (utils.go:84-90), whatever the strategy
+    if ((amask >> T & 1u) && ax->request[T] > 100 && ax->request[T] % 100 != 0) {
+      ch->early = true;
+      ch->fail_code = GS_EXT_FAIL_POD;
+      return GS_OK;
+    }
   if (ds_on && gpu_request_of(e, greq, &gmask) < 0) {   // DeviceShare PreFilter: UnschedulableAndUnresolvable
     ch->early = true;
     ch->fail_code = GS_EXT_FAIL_POD;
@@ -2173,6 +2353,7 @@ int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, E
   const auto hx0 = hx_clk::now();
   if ((rc = ext_alloc(c))) return rc;
   if ((rc = ext_flush_devices(c))) return rc;
+  if (amask && ((rc = ext_aux_alloc(c)) || (rc = ext_flush_aux(c)))) return rc;
   if ((rc = flush_rows(c))) return rc;
   if (c->prep_stale && (rc = node_prep(c))) return rc;
   const auto hx1 = hx_clk::now();
@@ -2268,6 +2449,14 @@ int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, E
   xp.rs_on = rs_on;
   xp.dev_most = c->ext.device_scoring_type == GS_SCORING_MOST_ALLOCATED;
   xp.seq = seq;
+  xp.aux_mask = amask;
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T)
+    if (amask >> T & 1u) {
+      xp.aux_req[T] = ax->request[T];
+      xp.aux_strategy[T] = ax->strategy[T];
+      xp.aux_excl[T] = ax->device_exclusive[T] ? 1 : 0;
+      xp.aux_w[T] = c->aux_weights[T];
+    }
   // GPU names are scalar requests: the Fit filter's all-zero short cut no longer applies
   if (gpu_names_all || xres_all) v.flags &= ~PF_ALL_ZERO;
   *reinterpret_cast<PodVec*>(c->h_xin.get() + ((sizeof(ExtPod) + 15) & ~(size_t)15)) = v;
@@ -2310,7 +2499,12 @@ int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, E
                          c->xnuma_n, d_aff, st));
   if (ext_ev) HIP_TRY(c, hipEventRecord(sl.ev[1].get(), st));
   // (ext_nodes_kernel also resets the select accumulators; ext_matched runs for pods with matched reservations only)
-  HIP_TRY(c, launch_ext_nodes(d_dev, d_S, c->n0, c->n1, c->d_xpod, d_xtot, d_xds, d_xrs, d_xT, st));
+  // (the refusals above keep an RDMA / FPGA pod away from ext_numa_kernel and ext_matched_kernel, which do not read the
+  // aux image)
+  if (amask && (nrec || (c->numa_on && c->xnuma_n)))
+    return fail(c, GS_ESTATE, "an RDMA / FPGA pod reached the matched-reservation or NUMA-policy kernels");
+  HIP_TRY(c, launch_ext_nodes(d_dev, amask ? c->d_aux.get() : nullptr, d_S, c->n0, c->n1, c->d_xpod, d_xtot, d_xds, d_xrs,
+                              d_xT, st));
   // GPU pods on NUMA-policy nodes: DeviceShare is the topology manager's second hint provider
   if (gmask && c->numa_on && c->xnuma_n)
     HIP_TRY(c, launch_ext_numa(c->mv, c->d_xpv, c->pf, prod_cols, d_dev, c->d_xpod, c->d_xnuma_idx.get(), c->xnuma_n,
@@ -2344,13 +2538,14 @@ int ext_chain(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, E
 
 // scheduleOne of one extension pod: the device chain (ext_chain), then the Reserve of NodeNUMAResource (no-op on the
 // supported nodes), DeviceShare and Reservation, and assume.
-int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t seq, gs_placement* out,
-                     gs_ext_placement* eo) {
+int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, const gs_pod_aux* ax, uint64_t seq,
+                     gs_placement* out, gs_ext_placement* eo, gs_aux_placement* ao) {
   *out = gs_placement{-1, 0, 0, 0, 0};
   *eo = gs_ext_placement{};
+  *ao = gs_aux_placement{};
   ExtChain ch;
   int rc;
-  if ((rc = ext_chain(c, pod, e, seq, &ch))) return rc;
+  if ((rc = ext_chain(c, pod, e, ax, seq, &ch))) return rc;
   if (ch.early) {
     eo->fail_code = ch.fail_code;
     c->stats.pods += 1;
@@ -2399,14 +2594,36 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
   }
   ExtReserved done{};   // what the Reserves below apply
   done.node = node;
-  if (gmask && (rc = ext_device_reserve(c, node, greq, gmask, eo, xo.aff, &done.gpu_keys))) {
-    // the reference runs every plugin's Unreserve on a Reserve failure: NodeNUMAResource's allocation goes again
+  // the reference runs every plugin's Unreserve on a Reserve failure: NodeNUMAResource's allocation goes again
+  const auto undo_numa = [&]() {
     if (c->numa_on && c->numa_uid_node.count(pod.uid)) {
       numa_release(c->numa[node], pod.uid);
       c->numa_uid_node.erase(pod.uid);
       mark_dirty(c, node);
     }
+  };
+  if (gmask && (rc = ext_device_reserve(c, node, greq, gmask, eo, xo.aff, &done.gpu_keys))) {
+    undo_numa();
     return rc;
+  }
+  // the RDMA / FPGA types after the GPU type (a node without a Device object allocates nothing, as for GPUs)
+  if (ch.amask && c->devs[node].has_device) {
+    gs_node_aux_devices row = c->aux.empty() ? gs_node_aux_devices{} : c->aux[node];   // (applied only when every type fits)
+    bool ok = true;
+    for (int T = 0; ok && T < GS_NUM_AUX_TYPES; ++T)
+      if (ch.amask >> T & 1u)
+        ok = aux_reserve_row(&row, T, ax->request[T], ax->strategy[T], ax->device_exclusive[T] ? 1 : 0, c->aux_weights[T],
+                             c->ext.device_scoring_type == GS_SCORING_MOST_ALLOCATED, ao);
+    if (!ok) {   // ... and the GPU minors just reserved
+      gpu_unreserve_row(&c->devs[node], eo->gpu_minor_mask, done.gpu_keys, eo->gpu_per_instance);
+      dev_mark(c, node);
+      undo_numa();
+      return fail(c, GS_ESTATE, "DeviceShare Reserve: RDMA / FPGA allocation failed on node %u after a feasible Filter",
+                  node);
+    }
+    c->aux[node] = row;
+    aux_mark(c, node);
+    done.aux = *ao;
   }
   int rec_i = -1;   // the chosen node's matched record (records are in node order)
   {
@@ -2441,7 +2658,7 @@ int ext_schedule_one(gs_ctx* c, const gs_pod& pod, const gs_pod_ext& e, uint64_t
       done.xres_req[x] = e.xres_requests[x];
       dev_mark(c, node);
     }
-  if (gmask || (rs_on && rec_i >= 0 && h_xnom[rec_i] >= 0) || gpu_names_all || xres_all) {
+  if (gmask || (rs_on && rec_i >= 0 && h_xnom[rec_i] >= 0) || gpu_names_all || xres_all || ch.amask) {
     done.gpu_minor_mask = eo->gpu_minor_mask;
     done.gpu_count = eo->gpu_count;
     for (int r = 0; r < GS_NUM_GPU_RES; ++r) done.gpu_per_instance[r] = eo->gpu_per_instance[r];
@@ -2482,7 +2699,8 @@ void gs_abi_sizes(uint64_t* out, uint32_t n) {
                         sizeof(gs_status_map), sizeof(gs_resident_pod), sizeof(gs_preemptor),
                         sizeof(gs_preempt_result), sizeof(gs_preempt_detail), sizeof(gs_preempt_candidate),
                         sizeof(gs_preempt_result_pdb), sizeof(gs_preempt_detail_pdb), sizeof(gs_preempt_candidate_pdb),
-                        sizeof(gs_top_score), sizeof(gs_top_scores)};
+                        sizeof(gs_top_score), sizeof(gs_top_scores), sizeof(gs_aux_device),
+                        sizeof(gs_node_aux_devices), sizeof(gs_pod_aux), sizeof(gs_aux_placement)};
   for (uint32_t i = 0; i < n && i < sizeof(s) / sizeof(s[0]); ++i) out[i] = s[i];
 }
 
@@ -2932,13 +3150,12 @@ int gs_pods_forget(gs_ctx* c, const uint32_t* node_idx, const gs_pod* pods, uint
       gs_node_devices& d = c->devs[i];
       // DeviceShare Unreserve: SubtractWithNonNegativeResult on the minors the Device row still has (a node without a
       // Device object now: getNodeDevice == nil, nothing to do)
-      if (d.has_device && x.gpu_minor_mask)
-        for (int g = 0; g < d.num_gpus; ++g) {
-          if (d.gpus[g].minor < 0 || d.gpus[g].minor > 31 || !(x.gpu_minor_mask >> d.gpus[g].minor & 1u)) continue;
-          for (int r = 0; r < GS_NUM_GPU_RES; ++r)
-            if (x.gpu_keys >> r & 1u)
-              d.gpus[g].used[r] = std::max<int64_t>(0, d.gpus[g].used[r] - x.gpu_per_instance[r]);
-        }
+      if (d.has_device && x.gpu_minor_mask) gpu_unreserve_row(&d, x.gpu_minor_mask, x.gpu_keys, x.gpu_per_instance);
+      // ... and on the RDMA / FPGA minors the aux row still has
+      if (d.has_device && !c->aux.empty() && (x.aux.minor_mask[0] | x.aux.minor_mask[1])) {
+        aux_unreserve_row(&c->aux[i], x.aux);
+        aux_mark(c, i);
+      }
       // Reservation Unreserve: the subtraction keeps a zero-valued key, so allocated_mask stays; a reservation deleted
       // since is skipped (forgetPod finds no rInfo)
       if (x.reservation_uid) {
@@ -4467,8 +4684,11 @@ int gs_reset(gs_ctx* c) {
   c->numa_idx_stale = c->xnuma_stale = true;
   if (c->d_dev)
     for (uint32_t i = 0; i < c->N; ++i) dev_mark(c, i);
+  if (c->d_aux)
+    for (uint32_t i = 0; i < c->N; ++i) aux_mark(c, i);
   int rc = flush_rows(c);
   if (!rc) rc = ext_flush_devices(c);
+  if (!rc) rc = ext_flush_aux(c);
   if (rc) return rc;
   if ((rc = node_prep(c))) return rc;
   if (c->pre) c->pre->rebuild = true;   // the resident-pod image: rebuilt from the host table by the next dry run
@@ -4728,9 +4948,9 @@ int gs_ext_reserved_get(gs_ctx* c, uint64_t uid, uint32_t* node, gs_ext_placemen
   return 1;
 }
 
-int gs_schedule_ext(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
-                    gs_placement* out, gs_ext_placement* ext_out) {
-  if (!c || (npods && (!pods || !out))) return GS_EINVAL;
+int gs_schedule_ext_aux(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, const gs_pod_aux* aux, uint32_t npods,
+                        const uint64_t* seq, gs_placement* out, gs_ext_placement* ext_out, gs_aux_placement* aux_out) {
+  if (!c || (npods && (!pods || !out)) || (aux && !ext)) return GS_EINVAL;
   quiesce(c);
   int rc = ready(c);
   if (rc) return rc;
@@ -4741,7 +4961,9 @@ int gs_schedule_ext(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, uint32
     // a run of plain pods goes through the batched path (both plugins score 0 for them; the mirror rows carry the
     // unmatched restore), an extension pod through the normalizing path
     uint32_t j = i;
-    while (j < npods && !(ext && (c->ext.enabled || ext[j].xres_request_mask) && is_ext_pod(c, ext[j]))) ++j;
+    while (j < npods && !(ext && (c->ext.enabled || ext[j].xres_request_mask) &&
+                          is_ext_pod(c, ext[j], aux ? &aux[j] : nullptr)))
+      ++j;
     if (j > i) {
       std::vector<uint64_t> sq;
       if (!seq) { sq.resize(j - i); for (uint32_t k = i; k < j; ++k) sq[k - i] = k; }
@@ -4752,23 +4974,84 @@ int gs_schedule_ext(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, uint32
         c->hx_runs += 1;
       }
       if (ext_out) std::memset(ext_out + i, 0, sizeof(gs_ext_placement) * (j - i));
+      if (aux_out) std::memset(aux_out + i, 0, sizeof(gs_aux_placement) * (j - i));
       i = j;
       continue;
     }
     gs_ext_placement eo{};
-    if ((rc = ext_schedule_one(c, pods[i], ext[i], seq ? seq[i] : i, &out[i], &eo))) return rc;
+    gs_aux_placement ao{};
+    if ((rc = ext_schedule_one(c, pods[i], ext[i], aux ? &aux[i] : nullptr, seq ? seq[i] : i, &out[i], &eo, &ao)))
+      return rc;
     if (ext_out) ext_out[i] = eo;
+    if (aux_out) aux_out[i] = ao;
     ++i;
   }
   rc = flush_rows(c);
   if (!rc) rc = ext_flush_devices(c);
+  if (!rc) rc = ext_flush_aux(c);
   return rc;
+}
+
+int gs_schedule_ext(gs_ctx* c, const gs_pod* pods, const gs_pod_ext* ext, uint32_t npods, const uint64_t* seq,
+                    gs_placement* out, gs_ext_placement* ext_out) {
+  return gs_schedule_ext_aux(c, pods, ext, nullptr, npods, seq, out, ext_out, nullptr);
+}
+
+int gs_ext_configure_aux(gs_ctx* c, const int64_t weights[GS_NUM_AUX_TYPES]) {
+  if (!c || !weights) return GS_EINVAL;
+  quiesce(c);
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T)
+    if (weights[T] < 0 || weights[T] > 100) return fail(c, GS_EINVAL, "DeviceShare weight out of range");
+  for (int T = 0; T < GS_NUM_AUX_TYPES; ++T) c->aux_weights[T] = weights[T];
+  return GS_OK;
+}
+
+int gs_node_aux_devices_upsert(gs_ctx* c, const uint32_t* idx, const gs_node_aux_devices* d, uint32_t n) {
+  if (!c || (n && !d)) return GS_EINVAL;
+  quiesce(c);
+  for (uint32_t k = 0; k < n; ++k) {   // (validated like gs_node_devices_upsert's GPUs)
+    const uint32_t i = idx ? idx[k] : k;
+    if (i >= c->N) return fail(c, GS_EINVAL, "node index %u out of range", i);
+    for (int T = 0; T < GS_NUM_AUX_TYPES; ++T) {
+      if (d[k].num[T] < 0 || d[k].num[T] > GS_MAX_AUX_DEVICES) return fail(c, GS_EINVAL, "RDMA / FPGA device count out of range");
+      for (int g = 0; g < d[k].num[T]; ++g) {
+        const gs_aux_device& x = d[k].dev[T][g];
+        for (int h = 0; h < g; ++h)
+          if (d[k].dev[T][h].minor == x.minor) return fail(c, GS_EINVAL, "duplicate RDMA / FPGA minor on node %u", i);
+        if (x.minor < 0 || x.minor > 31) return fail(c, GS_EUNSUPPORTED, "RDMA / FPGA minor outside 0..31");
+        if (x.numa_node < -1) return fail(c, GS_EINVAL, "RDMA / FPGA numa_node below -1");
+        if (x.total < 0 || x.used < 0 || x.total >= (1LL << 53) || x.used >= (1LL << 53))
+          return fail(c, GS_EUNSUPPORTED, "RDMA / FPGA quantity outside [0, 2^53)");
+      }
+    }
+    if (c->aux.empty()) c->aux.assign(c->N, gs_node_aux_devices{});
+    c->aux[i] = d[k];
+    aux_mark(c, i);
+  }
+  return GS_OK;
+}
+
+int gs_node_aux_devices_get(gs_ctx* c, uint32_t node, gs_node_aux_devices* out) {
+  if (!c || !out || node >= c->N) return GS_EINVAL;
+  quiesce(c);
+  *out = c->aux.empty() ? gs_node_aux_devices{} : c->aux[node];
+  return GS_OK;
+}
+
+int gs_ext_aux_reserved_get(gs_ctx* c, uint64_t uid, uint32_t* node, gs_aux_placement* out) {
+  if (!c || !node || !out) return GS_EINVAL;
+  quiesce(c);
+  auto it = c->ext_reserved.find(uid);
+  if (it == c->ext_reserved.end()) return 0;
+  *node = it->second.node;
+  *out = it->second.aux;
+  return 1;
 }
 
 // The per-node view of one extension pod: ext_schedule_one's device chain, then the rows it left in HBM. Nothing is
 // reserved or assumed.
-int gs_debug_ext_rows(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
-                      uint64_t* nominated_uid, int64_t* result) {
+int gs_debug_ext_rows_aux(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, const gs_pod_aux* aux, uint64_t seq,
+                          int32_t* rows, uint64_t* nominated_uid, int64_t* result) {
   if (!c || !pod || !ext || !rows || !nominated_uid || !result) return GS_EINVAL;
   quiesce(c);
   int rc = ready(c);
@@ -4785,7 +5068,7 @@ int gs_debug_ext_rows(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, uint6
   for (int k = 0; k < GS_EXT_ROWS_RESULT_WORDS; ++k) result[k] = 0;
   result[GS_EXT_ROWS_NODE] = result[GS_EXT_ROWS_PREF_NODE] = -1;
   ExtChain ch;
-  if ((rc = ext_chain(c, *pod, *ext, seq, &ch))) return rc;
+  if ((rc = ext_chain(c, *pod, *ext, aux, seq, &ch))) return rc;
   if (ch.early) {
     result[GS_EXT_ROWS_FAIL_CODE] = ch.fail_code;
     return GS_OK;
@@ -4821,6 +5104,11 @@ int gs_debug_ext_rows(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, uint6
   result[GS_EXT_ROWS_DS_NORM] = xo.node >= 0 ? xo.ds_norm : 0;
   result[GS_EXT_ROWS_RS_NORM] = xo.node >= 0 ? xo.rs_norm : 0;
   return GS_OK;
+}
+
+int gs_debug_ext_rows(gs_ctx* c, const gs_pod* pod, const gs_pod_ext* ext, uint64_t seq, int32_t* rows,
+                      uint64_t* nominated_uid, int64_t* result) {
+  return gs_debug_ext_rows_aux(c, pod, ext, nullptr, seq, rows, nominated_uid, result);
 }
 
 }  // extern "C"

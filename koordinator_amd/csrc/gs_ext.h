@@ -39,6 +39,20 @@ struct DevNode {                // gs_node_devices, as the kernels read it
 };
 static_assert(sizeof(DevNode) == 8 + 8 * EXT_FIT_NAMES + EXT_GPUS * 56, "DevNode layout");
 
+// The RDMA / FPGA devices of a node (gs_node_aux_devices), in an array of their own beside DevNode: ext_nodes_kernel
+// reads it only for a pod requesting one of the types
+struct DevAux {
+  int64_t total;
+  int64_t free;                 // max(0, total - used)
+  int32_t minor;
+  int32_t has_info;
+};
+struct DevAuxNode {
+  int32_t num[GS_NUM_AUX_TYPES];            // len(deviceTotal[type]): unhealthy and info-less entries included
+  DevAux d[GS_NUM_AUX_TYPES][GS_MAX_AUX_DEVICES];
+};
+static_assert(sizeof(DevAuxNode) == 8 + GS_NUM_AUX_TYPES * GS_MAX_AUX_DEVICES * 24, "DevAuxNode layout");
+
 struct ExtRes {                 // one matched reservation (ReservationInfo fields the Filter / Score read)
   int64_t alloc[7];             // Allocatable per slot (0 where absent)
   int64_t allocated[7];
@@ -77,6 +91,13 @@ struct ExtPod {                 // per-pod constants of the three kernels
   int32_t ds_on, rs_on;
   int32_t dev_most;
   uint64_t seq;
+  // RDMA / FPGA (gs_pod_aux): bit T of aux_mask = the pod requests type T
+  int64_t aux_req[GS_NUM_AUX_TYPES];
+  int64_t aux_w[GS_NUM_AUX_TYPES];          // the type's ScoringStrategy weight
+  int32_t aux_strategy[GS_NUM_AUX_TYPES];
+  int32_t aux_excl[GS_NUM_AUX_TYPES];
+  uint32_t aux_mask;
+  uint32_t pad;
 };
 
 struct ExtOut {
@@ -98,8 +119,9 @@ struct ExtOut {
 };
 
 // (also resets the select accumulators in `scratch`, launch_ext_select's scratch of n1 - n0 nodes)
-hipError_t launch_ext_nodes(const DevNode* dev, const int16_t* S, uint32_t n0, uint32_t n1, const ExtPod* pod,
-                            int32_t* tot, int16_t* ds, int16_t* rs, int32_t* scratch, hipStream_t st);
+// aux: the DevAuxNode array (read only when the pod requests RDMA / FPGA; may be null otherwise)
+hipError_t launch_ext_nodes(const DevNode* dev, const DevAuxNode* aux, const int16_t* S, uint32_t n0, uint32_t n1,
+                            const ExtPod* pod, int32_t* tot, int16_t* ds, int16_t* rs, int32_t* scratch, hipStream_t st);
 hipError_t launch_ext_matched(const MirrorView& m, const PodVec* pods, const Profile& pf, int prod_cols,
                               const DevNode* dev, const ExtPod* pod, const ExtRec* recs, const ExtRes* res, int nrec, int32_t* tot,
                               int16_t* ds, int16_t* rs, int32_t* nominated, uint8_t* aff, uint32_t n0, int32_t* scratch,
@@ -120,6 +142,8 @@ hipError_t launch_ext_finish(const MirrorView& m, const PodVec* pods, const Prof
 size_t ext_select_scratch_words(uint32_t len);   // int32 words of launch_ext_select's scratch
 // dev[idx[j]] = img[j], j < n (staged Device image updates)
 hipError_t launch_scatter_devnodes(DevNode* dev, const uint32_t* idx, const DevNode* img, uint32_t n, hipStream_t st);
+hipError_t launch_scatter_auxnodes(DevAuxNode* aux, const uint32_t* idx, const DevAuxNode* img, uint32_t n,
+                                   hipStream_t st);
 hipError_t launch_ext_select(const int32_t* tot, const int16_t* ds, const int16_t* rs, const ExtRec* recs, uint32_t n0,
                              uint32_t n1, const ExtPod* pod, uint64_t seed, int32_t* scratch, ExtOut* out,
                              hipStream_t st);

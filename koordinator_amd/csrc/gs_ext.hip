@@ -3,6 +3,7 @@
 // Reference: deviceshare/plugin.go:272-322 (Filter), deviceshare/scoring.go:34-89,186-308 (Score),
 // deviceshare/device_allocator.go:99-163,397-467,513-536 (Allocate / score), devicehandler_gpu.go:38-85 (desired
 // per-instance request), reservation/transformer.go:50-292 (restore), reservation/plugin.go:311-496 (Filter, fitsNode),
+// devicehandler_default.go:44-93 (RDMA / FPGA per-instance request and count), device_cache.go:344-395 (nodeDevice.filter),
 // reservation/nominator.go:140-190 + scoring.go:42-203 (nomination, PreScore, Score),
 // [upstream] pluginhelper.DefaultNormalizeScore, schedule_one.go selectHost.
 #include <hip/hip_runtime.h>
@@ -70,12 +71,10 @@ __device__ __forceinline__ bool on_aff(const DevGpu& x, uint32_t aff) {
   return !(aff & 0x10u) || (x.zone >= 0 && (aff >> x.zone & 1u));
 }
 
-__device__ __forceinline__ void eval_device(const DevNode& d, const ExtPod& p, bool* ok, int32_t* raw,
-                                            uint32_t aff = 0) {
+// the GPU type on one node with a Device object: Prepare, the candidates, the allocation, scoreNode
+__device__ __forceinline__ void eval_gpu_type(const DevNode& d, const ExtPod& p, bool* ok, int32_t* raw, uint32_t aff) {
   *ok = true;
   *raw = 0;
-  if (!fit_names_ok(d, p)) { *ok = false; return; }
-  if (!d.has_device || !p.gpu_mask) return;   // no Device object / no GPU request: DeviceShare passes, scores 0
   int64_t inst[3];
   uint32_t mask;
   int64_t count;
@@ -106,10 +105,74 @@ __device__ __forceinline__ void eval_device(const DevNode& d, const ExtPod& p, b
   *raw = ws ? (int32_t)(ns / ws) : 0;
 }
 
+// One RDMA / FPGA type T on one node (DefaultDeviceHandler.CalcDesiredRequestsAndCount, devicehandler_default.go:44-93;
+// filterNodeDevice, device_allocator.go:139-163 -> nodeDevice.filter, device_cache.go:344-395; defaultAllocateDevices,
+// device_allocator.go:397-467; scoreNode, scoring.go:213-243). false: the node fails
+__device__ __forceinline__ bool eval_aux_type(const DevAuxNode& a, const ExtPod& p, int T, int32_t* raw) {
+  const int n = a.num[T];
+  if (n <= 0) return false;   // Prepare: "Insufficient rdma devices" (an unhealthy entry is enough to pass)
+  const int64_t q = p.aux_req[T];
+  int64_t inst = q, count = 1;
+  if (q > 100 && q % 100 == 0) { count = q / 100; inst = 100; }   // (the hint is ignored)
+  else if (p.aux_strategy[T] == GS_AUX_APPLY_FOR_ALL) count = n;
+  else if (p.aux_strategy[T] == GS_AUX_REQUESTS_AS_COUNT) { count = q; inst = p.aux_excl[T] ? 100 : 1; }
+  // nodeDevice.filter: a type whose devices are all fully used is dropped
+  bool all_zero = true;
+  for (int k = 0; k < n; ++k) all_zero &= a.d[T][k].free == 0;
+  if (all_zero) return false;
+  int64_t ok_n = 0, tot = 0, fr = 0;
+  for (int k = 0; k < n; ++k) {
+    const DevAux& x = a.d[T][k];
+    if (!x.has_info) continue;
+    tot += x.total;
+    fr += x.free;
+    if (x.free != 0 && inst <= x.free) ++ok_n;
+  }
+  if (ok_n < count) return false;
+  if (p.aux_w[T] && tot != 0) {   // one resource name: the weighted mean is the resource's own score
+    int64_t rq = tot;
+    if (tot >= fr) rq = tot - fr + inst;
+    *raw = (int32_t)(p.dev_most ? ds_most(rq, tot) : ds_least(rq, tot));
+  } else {
+    *raw = 0;
+  }
+  return true;
+}
+
+// a: the node's RDMA / FPGA devices, given only for a pod requesting one of the types (every requested type must
+// allocate; AutopilotAllocator.score sums scoreNode over the types, device_allocator.go:513-536)
+__device__ __forceinline__ void eval_device(const DevNode& d, const ExtPod& p, bool* ok, int32_t* raw,
+                                            uint32_t aff = 0, const DevAuxNode* a = nullptr) {
+  *ok = true;
+  *raw = 0;
+  if (!fit_names_ok(d, p)) { *ok = false; return; }
+  if (!d.has_device) return;                  // no Device object: DeviceShare passes, scores 0
+  if (a) {
+    int32_t sum = 0;
+    for (int T = 0; T < GS_NUM_AUX_TYPES; ++T) {
+      if (!(p.aux_mask >> T & 1u)) continue;
+      int32_t r = 0;
+      if (!eval_aux_type(*a, p, T, &r)) { *ok = false; return; }
+      sum += r;
+    }
+    if (p.gpu_mask) {
+      int32_t g = 0;
+      eval_gpu_type(d, p, ok, &g, aff);
+      sum += g;
+    }
+    if (*ok) *raw = sum;
+    return;
+  }
+  if (!p.gpu_mask) return;                    // no GPU request: DeviceShare passes, scores 0
+  eval_gpu_type(d, p, ok, raw, aff);
+}
+
 constexpr int ACC_WORDS_N = 8;   // (ACC_* below)
-__global__ __launch_bounds__(256) void ext_nodes_kernel(const DevNode* __restrict__ dev, const int16_t* __restrict__ S,
-                                                         uint32_t n0, uint32_t n1, const ExtPod* __restrict__ pp,
-                                                         int32_t* tot, int16_t* ds, int16_t* rs, int32_t* acc) {
+__global__ __launch_bounds__(256) void ext_nodes_kernel(const DevNode* __restrict__ dev,
+                                                         const DevAuxNode* __restrict__ aux,
+                                                         const int16_t* __restrict__ S, uint32_t n0, uint32_t n1,
+                                                         const ExtPod* __restrict__ pp, int32_t* tot, int16_t* ds,
+                                                         int16_t* rs, int32_t* acc) {
   // the select accumulators start from zero (ACC_PREF: -1, no preferred node unless ext_matched_kernel finds one)
   if (blockIdx.x == 0 && threadIdx.x < ACC_WORDS_N) acc[threadIdx.x] = threadIdx.x == 6 ? -1 : 0;
   const uint32_t i = n0 + blockIdx.x * 256 + threadIdx.x;
@@ -117,9 +180,9 @@ __global__ __launch_bounds__(256) void ext_nodes_kernel(const DevNode* __restric
   const ExtPod& p = *pp;
   int32_t t = S[i - n0];
   int32_t raw = 0;
-  if (t >= 0 && (p.gpu_mask || p.gpu_names)) {
+  if (t >= 0 && (p.gpu_mask || p.gpu_names || p.aux_mask)) {
     bool ok;
-    eval_device(dev[i], p, &ok, &raw);
+    eval_device(dev[i], p, &ok, &raw, 0, p.aux_mask ? &aux[i] : nullptr);
     if (!ok) t = -1;
   }
   if (p.required) t = -1;       // reservation affinity: only nodes with a matched reservation (ext_matched_kernel)
@@ -581,7 +644,24 @@ __global__ __launch_bounds__(256) void scatter_devnodes_kernel(DevNode* dev, con
   reinterpret_cast<int64_t*>(dev + idx[j])[w] = reinterpret_cast<const int64_t*>(img + j)[w];
 }
 
+constexpr int AUX_WORDS = (int)(sizeof(DevAuxNode) / 8);
+static_assert(sizeof(DevAuxNode) % 8 == 0, "DevAuxNode words");
+__global__ __launch_bounds__(256) void scatter_auxnodes_kernel(DevAuxNode* aux, const uint32_t* __restrict__ idx,
+                                                               const DevAuxNode* __restrict__ img, uint32_t n) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n * AUX_WORDS) return;
+  const uint32_t j = t / AUX_WORDS, w = t % AUX_WORDS;
+  reinterpret_cast<int64_t*>(aux + idx[j])[w] = reinterpret_cast<const int64_t*>(img + j)[w];
+}
+
 }  // namespace
+
+hipError_t launch_scatter_auxnodes(DevAuxNode* aux, const uint32_t* idx, const DevAuxNode* img, uint32_t n,
+                                   hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(scatter_auxnodes_kernel, dim3((n * AUX_WORDS + 255) / 256), dim3(256), 0, st, aux, idx, img, n);
+  return hipGetLastError();
+}
 
 hipError_t launch_scatter_devnodes(DevNode* dev, const uint32_t* idx, const DevNode* img, uint32_t n, hipStream_t st) {
   if (!n) return hipSuccess;
@@ -589,11 +669,11 @@ hipError_t launch_scatter_devnodes(DevNode* dev, const uint32_t* idx, const DevN
   return hipGetLastError();
 }
 
-hipError_t launch_ext_nodes(const DevNode* dev, const int16_t* S, uint32_t n0, uint32_t n1, const ExtPod* pod,
-                            int32_t* tot, int16_t* ds, int16_t* rs, int32_t* scratch, hipStream_t st) {
+hipError_t launch_ext_nodes(const DevNode* dev, const DevAuxNode* aux, const int16_t* S, uint32_t n0, uint32_t n1,
+                            const ExtPod* pod, int32_t* tot, int16_t* ds, int16_t* rs, int32_t* scratch, hipStream_t st) {
   const uint32_t len = n1 - n0;
-  hipLaunchKernelGGL(ext_nodes_kernel, dim3(len ? (len + 255) / 256 : 1), dim3(256), 0, st, dev, S, n0, n1, pod, tot,
-                     ds, rs, scratch + len);
+  hipLaunchKernelGGL(ext_nodes_kernel, dim3(len ? (len + 255) / 256 : 1), dim3(256), 0, st, dev, aux, S, n0, n1, pod,
+                     tot, ds, rs, scratch + len);
   return hipGetLastError();
 }
 

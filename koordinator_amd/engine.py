@@ -415,6 +415,65 @@ class Engine:
         self._chk(min(rc, 0), "gs_ext_reserved_get")
         return (int(node.value), out[0]) if rc == 1 else None
 
+    # ---- DeviceShare device types beyond GPU: RDMA and FPGA
+    def ext_configure_aux(self, weights):
+        """ScoringStrategy.Resources weights of koordinator.sh/rdma and koordinator.sh/fpga (default 0, 0)"""
+        w = np.ascontiguousarray(weights, dtype=np.int64)
+        assert len(w) == abi.GS_NUM_AUX_TYPES
+        self._chk(lib().gs_ext_configure_aux(self._h, abi.ptr(w)), "gs_ext_configure_aux")
+
+    def upsert_aux_devices(self, devs, idx=None):
+        devs = np.ascontiguousarray(devs, dtype=abi.NODE_AUX_DEVICES_DTYPE)
+        if idx is not None:
+            idx = np.ascontiguousarray(idx, dtype=np.uint32)
+        self._chk(lib().gs_node_aux_devices_upsert(self._h, abi.ptr(idx), abi.ptr(devs), len(devs)),
+                  "gs_node_aux_devices_upsert")
+
+    def aux_devices(self, node: int):
+        out = np.zeros(1, abi.NODE_AUX_DEVICES_DTYPE)
+        self._chk(lib().gs_node_aux_devices_get(self._h, node, abi.ptr(out)), "gs_node_aux_devices_get")
+        return out[0]
+
+    def schedule_ext_aux(self, pods, ext, aux=None, seq=None):
+        """gs_schedule_ext_aux: (placements, EXT_PLACEMENT_DTYPE, AUX_PLACEMENT_DTYPE records); aux None = schedule_ext"""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        ext = np.ascontiguousarray(ext, dtype=abi.POD_EXT_DTYPE)
+        assert len(ext) == len(pods)
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, dtype=abi.POD_AUX_DTYPE)
+            assert len(aux) == len(pods)
+        if seq is None:
+            seq = np.arange(len(pods), dtype=np.uint64)
+        seq = np.ascontiguousarray(seq, dtype=np.uint64)
+        out = np.zeros(len(pods), abi.PLACEMENT_DTYPE)
+        eo = np.zeros(len(pods), abi.EXT_PLACEMENT_DTYPE)
+        ao = np.zeros(len(pods), abi.AUX_PLACEMENT_DTYPE)
+        self._chk(lib().gs_schedule_ext_aux(self._h, abi.ptr(pods), abi.ptr(ext), abi.ptr(aux), len(pods), abi.ptr(seq),
+                                            abi.ptr(out), abi.ptr(eo), abi.ptr(ao)), "gs_schedule_ext_aux")
+        return out, eo, ao
+
+    def ext_aux_reserved(self, uid: int):
+        """gs_ext_aux_reserved_get: (node, AUX_PLACEMENT_DTYPE record) of an assumed pod's recorded Reserve, or None"""
+        node = C.c_uint32(0)
+        out = np.zeros(1, abi.AUX_PLACEMENT_DTYPE)
+        rc = lib().gs_ext_aux_reserved_get(self._h, int(uid), C.byref(node), abi.ptr(out))
+        self._chk(min(rc, 0), "gs_ext_aux_reserved_get")
+        return (int(node.value), out[0]) if rc == 1 else None
+
+    def ext_rows_aux(self, pod, ext, aux, seq: int = 0) -> dict:
+        """ext_rows of a pod with RDMA / FPGA requests (gs_debug_ext_rows_aux): the same keys"""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        ext = np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        if aux is not None:
+            aux = np.ascontiguousarray(np.atleast_1d(aux), dtype=abi.POD_AUX_DTYPE)
+        n = self.cfg.num_nodes
+        rows = np.zeros((len(abi.EXT_ROW_KEYS), n), np.int32)
+        nom = np.zeros(n, np.uint64)
+        res = np.zeros(len(abi.EXT_ROWS_RESULT_KEYS), np.int64)
+        self._chk(lib().gs_debug_ext_rows_aux(self._h, abi.ptr(pod), abi.ptr(ext), abi.ptr(aux), int(seq), abi.ptr(rows),
+                                              abi.ptr(nom), abi.ptr(res)), "gs_debug_ext_rows_aux")
+        return abi.ext_rows_dict(rows, nom, res)
+
     # ---- NodeNUMAResource state
     def register_topology(self, topo) -> int:
         t = abi.GsCpuTopology.from_buffer_copy(np.ascontiguousarray(np.atleast_1d(topo), abi.TOPOLOGY_DTYPE).tobytes())
