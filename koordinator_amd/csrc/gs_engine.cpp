@@ -74,6 +74,24 @@ Vec2 usage_of(const gs_usage& u) {
   return o;
 }
 
+// The reports a batch's device pass computes behind its commit: the FitError diagnosis' wide pass (rows: with the
+// status rows), or the top-N score tables' pass (topn > 0). A run asks for one kind at most.
+struct ReportMode {
+  bool diag = false, rows = false;
+  uint32_t topn = 0;
+  bool any() const { return diag || topn; }
+};
+// Where a run's reports go (all null: a plain run computes none).
+struct Reports {
+  gs_fit_diagnosis* diag = nullptr;   // gs_schedule_diag: the FitError diagnosis of each pod
+  gs_status_map* map = nullptr;       // gs_schedule_diag_nodes: the per-node status rows of those pods (with diag)
+  gs_top_scores* top = nullptr;       // gs_schedule_top_scores: the top-N score table of each scored pod
+  uint32_t topn() const { return top ? top->topn : 0u; }
+  // whether the run's batches run the wide pass with the status rows (a map without rows keeps the counters-only kernels)
+  bool wants_rows() const { return diag && map && map->cap_rows; }
+  ReportMode mode() const { return ReportMode{diag != nullptr, wants_rows(), topn()}; }
+};
+
 // One of the two per-batch buffer sets: everything a batch in flight reads or writes on its own. While one slot's batch
 // commits, the next batch is staged and enqueued speculatively on the other slot (schedule_stream).
 struct Slot {
@@ -100,12 +118,12 @@ struct Slot {
   // the verdict on the batch's exchange tags (score rows: the slot's own, written by unpack_scores_kernel; levels:
   // merge_levels_kernel's, one block for both slots; one rank: none)
   int32_t* d_xerr = nullptr;
+  ReportMode rep;                   // the reports the slot's batch runs behind its commit (launch_batch)
   // FitError diagnosis (gs_schedule_diag; allocated by the context's first such run, alloc_diag)
-  bool diag_on = false;             // the slot's batch runs the wide pass behind its commit
   Event ev_dg;                      // the wide pass's end (a readback on st_rb waits for it)
   DevBuf<uint32_t> d_diag;          // [MAX_BATCH][DIAG_WORDS]: the wide pass's counters, read back with the placements
   PinnedBuf<uint32_t> h_diag;
-  // the landed pass of the slot's batch (diag_landed): one staged block (row versions | their slab indices | pod
+  // the landed pass of the slot's batch (landed_pass): one staged block (row versions | their slab indices | pod
   // vectors | version indices), the slab the versions are scattered into, and the pass's counters
   PinnedBuf<uint8_t> h_dgl;
   DevBuf<uint8_t> d_dgl;
@@ -114,7 +132,6 @@ struct Slot {
   DevBuf<uint32_t> d_ldiag;
   PinnedBuf<uint32_t> h_ldiag;
   // the diagnosis' status map (gs_schedule_diag_nodes; allocated by the context's first such run, alloc_map)
-  bool map_on = false;              // the slot's batch runs the wide pass's MAP instantiation
   DevBuf<uint16_t> d_words;         // [MAX_BATCH][npad]: row f = the batch's f-th pod with no node, in queue order
   PinnedBuf<uint16_t> h_words;      // the rows the host asked for (fetch_rows), same stride
   int rows_fetched = 0;             // rows of the slot's batch on their way to h_words (fetch_rows -> apply_batch)
@@ -123,7 +140,6 @@ struct Slot {
   DevBuf<uint16_t> d_lwords;        // [pod of the landed pass][landed node]: the landed pass's words
   PinnedBuf<uint16_t> h_lwords;
   // the top-N score tables (gs_schedule_top_scores; allocated by the context's first such run, alloc_top)
-  uint32_t top_n = 0;               // > 0: the slot's batch runs top_scores_kernel behind its commit, with this topn
   DevBuf<uint8_t> d_top;            // the pass's counts and rows (TOP_BYTES), read back with the placements
   PinnedBuf<uint8_t> h_top;
   DevBuf<TopLanded> d_ltop;         // [pod of the landed pass][landed node]: the landed pass's totals and plugin scores
@@ -166,9 +182,7 @@ struct AsyncRun {
   std::vector<gs_pod> pods;
   std::vector<uint64_t> seq;
   gs_placement* out = nullptr;
-  gs_fit_diagnosis* diag = nullptr;   // gs_schedule_submit_diag
-  gs_status_map* map = nullptr;       // gs_schedule_submit_diag_nodes
-  gs_top_scores* top = nullptr;       // gs_schedule_submit_top_scores
+  Reports rep;                        // gs_schedule_submit_diag / _diag_nodes / _top_scores
   uint64_t ticket = 0;
   int rc = 1;   // 1: not complete
   std::string err;
@@ -329,13 +343,13 @@ struct gs_ctx {
   bool host_timing = false;
   double ht_wait = 0, ht_apply = 0, ht_stage = 0, ht_launch = 0, ht_max_busy = 0;
   uint64_t ht_batches = 0, ht_busy_hist[8] = {};
-  // ... and of the FitError diagnosis: deriving the landed-row versions, the landed pass (upload to counters, waited for)
-  double hd_derive = 0, hd_landed = 0;
-  uint64_t hd_batches = 0, hd_versions = 0, hd_pods = 0;
+  // ... and of the batch reports, per kind ([0] FitError diagnosis, [1] top-N score tables): deriving the landed-row
+  // versions, the landed pass (upload to results, waited for), merging into the caller's buffers
+  struct ReportTiming {
+    double derive = 0, landed = 0, merge = 0;
+    uint64_t batches = 0, versions = 0, pods = 0;
+  } hr[2];
   uint64_t hd_map_rows = 0, hd_map_bytes = 0;   // status map: rows read back, and their bytes with the landed words'
-  // ... and of the top-N score tables: deriving the landed-row versions, the landed pass, merging into the caller's rows
-  double tp_derive = 0, tp_landed = 0, tp_merge = 0;
-  uint64_t tp_batches = 0, tp_versions = 0, tp_pods = 0;
   // ... and of gs_schedule_ext: per extension pod (records, flushes, the device chain up to the host's wake-up, the
   // Reserves) and per plain run (the whole gs_schedule call)
   double hx_prep = 0, hx_flush = 0, hx_gpu = 0, hx_reserve = 0, hx_plain = 0;
@@ -1503,42 +1517,10 @@ TopArgs top_args(const gs_ctx* c, const Slot& s, int b) {
   a.out = s.d_out;
   a.S = s.d_S.get();
   a.ld = c->ld;
-  a.topn = s.top_n;
+  a.topn = s.rep.topn;
   a.nbins = c->max_score + 1;
   a.top = s.d_top.get();
   return a;
-}
-
-// The landed pass of a batch's tables (blocking; off the commit stream), as diag_landed: nv row versions staged at
-// the head of s.h_dgl are scattered into the slot's slab, pod f (fpods[f]) is evaluated on versions vidx[f * nL ..],
-// and the nF x nL totals and plugin scores arrive in s.h_ltop.
-int top_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL) {
-  const int nF = (int)fpods.size();
-  const size_t off_idx = (size_t)nv * ROW_WORDS * 8;
-  const size_t off_pods = (off_idx + (size_t)nv * 4 + 7) & ~(size_t)7;
-  const size_t off_vidx = off_pods + sizeof(PodVec) * nF;
-  const size_t total = off_vidx + 2 * (size_t)nF * nL;
-  if (nv > DIAG_VERSIONS || total > DGL_BYTES) return fail(c, GS_ESTATE, "top scores: landed-row versions overflow");
-  uint8_t* h = s.h_dgl.get();
-  uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + off_idx);
-  for (int v = 0; v < nv; ++v) h_idx[v] = (uint32_t)v;
-  std::memcpy(h + off_pods, fpods.data(), sizeof(PodVec) * nF);
-  std::memcpy(h + off_vidx, vidx.data(), 2 * (size_t)nF * nL);
-  const hipStream_t st = c->st_dg.get();
-  uint8_t* d = s.d_dgl.get();
-  const MirrorView slab{s.dgl_i64.get(), s.dgl_i32.get(), (uint32_t)DIAG_VERSIONS};
-  const gs_loadaware_args& la = c->cfg.loadaware;
-  const ScatterPrep sp{c->now, la.filter_expired_node_metrics, la.has_node_metric_expiration,
-                       la.has_node_metric_expiration ? la.node_metric_expiration_seconds * 1000000000LL : 0};
-  HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
-  HIP_TRY(c, launch_scatter_rows(slab, reinterpret_cast<const uint32_t*>(d + off_idx), reinterpret_cast<const int64_t*>(d),
-                                 (uint32_t)nv, st, &sp));
-  HIP_TRY(c, launch_top_scores_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
-                                      reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ltop.get(), st));
-  HIP_TRY(c, hipMemcpyAsync(s.h_ltop.get(), s.d_ltop.get(), sizeof(TopLanded) * nF * nL, hipMemcpyDeviceToHost, st));
-  Where w_(c, "top_landed: the landed pass");
-  HIP_TRY(c, host_wait_stream(st));
-  return GS_OK;
 }
 
 DiagMapArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
@@ -1558,22 +1540,51 @@ DiagMapArgs diag_args(const gs_ctx* c, const Slot& s, int b) {
   return a;
 }
 
-// the wide pass of slot s's batch: the counters, and with s.map_on each counted pair's status word
-hipError_t launch_wide_pass(const Slot& s, const DiagMapArgs& a, hipStream_t st) {
-  return s.map_on ? launch_fit_diag_map(a, st) : launch_fit_diag(a, st);
+// The reports of slot s's batch of b pods (s.rep) behind its commit on st: the wide pass over counters zeroed first
+// (clear; force0: for pod 0 alone, which the host found unschedulable, on every node of the mirror), or the top-N
+// score tables' pass. rb: the stream of the batch's read-back, which waits for the pass.
+int launch_reports(gs_ctx* c, Slot& s, int b, hipStream_t st, hipStream_t rb, bool clear, bool force0 = false) {
+  if (s.rep.diag) {
+    if (clear) HIP_TRY(c, hipMemsetAsync(s.d_diag.get(), 0, DIAG_BYTES, st));
+    DiagMapArgs a = diag_args(c, s, b);
+    a.force0 = force0 ? 1 : 0;
+    HIP_TRY(c, s.rep.rows ? launch_fit_diag_map(a, st) : launch_fit_diag(a, st));
+  } else {
+    HIP_TRY(c, launch_top_scores(top_args(c, s, b), st));
+  }
+  if (rb != st) {
+    HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
+    HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
+  }
+  return GS_OK;
 }
 
+// ... and their read-back for the batch's first n pods, beside the placements': the wide pass's counters, or the counts
+// and rows of the tables
+int read_reports(gs_ctx* c, Slot& s, int n, hipStream_t rb) {
+  if (s.rep.diag)
+    HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * n, hipMemcpyDeviceToHost, rb));
+  else
+    HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_COUNT_BYTES + TOP_POD_BYTES * n, hipMemcpyDeviceToHost, rb));
+  return GS_OK;
+}
+
+// What the landed pass evaluates: the diagnosis' counters, those with the status words, or the top-N totals.
+enum class Landed { DIAG, DIAG_MAP, TOP };
+
 // The landed pass of a batch (blocking; off the commit stream): nv row versions staged at the head of s.h_dgl are
-// scattered into the slot's slab with their LoadAware verdicts at `now`, pod f (fpods[f]) is evaluated on versions
-// vidx[f * nL ..], and the nF pods' counters arrive in s.h_ldiag; map: their status words [f][nL] in s.h_lwords too.
-int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx, int nL,
-                bool map) {
+// scattered into the slot's slab with their LoadAware verdicts at `now`, and pod f (fpods[f]) is evaluated on versions
+// vidx[f * nL ..]. DIAG: the nF pods' counters arrive in s.h_ldiag; DIAG_MAP: their status words [f][nL] in s.h_lwords
+// too; TOP: the nF x nL totals and plugin scores in s.h_ltop.
+int landed_pass(gs_ctx* c, Slot& s, Landed kind, int nv, const std::vector<PodVec>& fpods, const std::vector<uint16_t>& vidx,
+                int nL) {
   const int nF = (int)fpods.size();
   const size_t off_idx = (size_t)nv * ROW_WORDS * 8;
   const size_t off_pods = (off_idx + (size_t)nv * 4 + 7) & ~(size_t)7;
   const size_t off_vidx = off_pods + sizeof(PodVec) * nF;
   const size_t total = off_vidx + 2 * (size_t)nF * nL;
-  if (nv > DIAG_VERSIONS || total > DGL_BYTES) return fail(c, GS_ESTATE, "FitError diagnosis: landed-row versions overflow");
+  if (nv > DIAG_VERSIONS || total > DGL_BYTES)
+    return fail(c, GS_ESTATE, "%s: landed-row versions overflow", kind == Landed::TOP ? "top scores" : "FitError diagnosis");
   uint8_t* h = s.h_dgl.get();
   uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + off_idx);
   for (int v = 0; v < nv; ++v) h_idx[v] = (uint32_t)v;
@@ -1588,17 +1599,21 @@ int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, co
   HIP_TRY(c, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, st));
   HIP_TRY(c, launch_scatter_rows(slab, reinterpret_cast<const uint32_t*>(d + off_idx), reinterpret_cast<const int64_t*>(d),
                                  (uint32_t)nv, st, &sp));
-  if (map) {
-    HIP_TRY(c, launch_fit_diag_landed_map(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
-                                          reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(),
-                                          s.d_lwords.get(), st));
-    HIP_TRY(c, hipMemcpyAsync(s.h_lwords.get(), s.d_lwords.get(), sizeof(uint16_t) * nF * nL, hipMemcpyDeviceToHost, st));
+  const PodVec* d_pods = reinterpret_cast<const PodVec*>(d + off_pods);
+  const uint16_t* d_vidx = reinterpret_cast<const uint16_t*>(d + off_vidx);
+  if (kind == Landed::TOP) {
+    HIP_TRY(c, launch_top_scores_landed(slab, d_pods, c->pf, d_vidx, nF, nL, s.d_ltop.get(), st));
+    HIP_TRY(c, hipMemcpyAsync(s.h_ltop.get(), s.d_ltop.get(), sizeof(TopLanded) * nF * nL, hipMemcpyDeviceToHost, st));
   } else {
-    HIP_TRY(c, launch_fit_diag_landed(slab, reinterpret_cast<const PodVec*>(d + off_pods), c->pf,
-                                      reinterpret_cast<const uint16_t*>(d + off_vidx), nF, nL, s.d_ldiag.get(), st));
+    if (kind == Landed::DIAG_MAP) {
+      HIP_TRY(c, launch_fit_diag_landed_map(slab, d_pods, c->pf, d_vidx, nF, nL, s.d_ldiag.get(), s.d_lwords.get(), st));
+      HIP_TRY(c, hipMemcpyAsync(s.h_lwords.get(), s.d_lwords.get(), sizeof(uint16_t) * nF * nL, hipMemcpyDeviceToHost, st));
+    } else {
+      HIP_TRY(c, launch_fit_diag_landed(slab, d_pods, c->pf, d_vidx, nF, nL, s.d_ldiag.get(), st));
+    }
+    HIP_TRY(c, hipMemcpyAsync(s.h_ldiag.get(), s.d_ldiag.get(), sizeof(uint32_t) * DIAG_WORDS * nF, hipMemcpyDeviceToHost, st));
   }
-  HIP_TRY(c, hipMemcpyAsync(s.h_ldiag.get(), s.d_ldiag.get(), sizeof(uint32_t) * DIAG_WORDS * nF, hipMemcpyDeviceToHost, st));
-  Where w_(c, "diag_landed: the landed pass");
+  Where w_(c, "landed_pass: the landed pass");
   HIP_TRY(c, host_wait_stream(st));
   return GS_OK;
 }
@@ -1608,11 +1623,10 @@ int diag_landed(gs_ctx* c, Slot& s, int nv, const std::vector<PodVec>& fpods, co
 // prev_b pods (prev: its committed words, prev_out: its placements): its eval pass runs beside that batch's commit, on
 // the mirror as it was before it, and the rows that batch landed on are re-evaluated on st once it committed (patch_kernel);
 // its commit kernel does nothing unless that batch committed every pod and needs no host-side Reserve (prev[1] == 1).
-// diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements; map: the
-// pass also leaves the status rows in the slot's d_words (fetch_rows reads back the ones the caller has room for).
-// topn > 0: the top-N score tables' pass behind the commit instead, its counts and rows read back with the placements.
-int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int prev_b = 0, bool diag = false,
-                 bool map = false, uint32_t topn = 0) {
+// rep.diag: the FitError diagnosis' wide pass behind the commit, its counters read back with the placements; rep.rows:
+// the pass also leaves the status rows in the slot's d_words (fetch_rows reads back the ones the caller has room for).
+// rep.topn > 0: the top-N score tables' pass behind the commit instead, its counts and rows read back with the placements.
+int launch_batch(gs_ctx* c, Slot& s, int b, ReportMode rep, const Slot* before = nullptr, int prev_b = 0) {
   const int32_t* prev = before ? before->d_committed.get() : nullptr;
   const PlacementDev* prev_out = before ? before->d_out : nullptr;
   const hipStream_t st = c->st.get(), st_ev = c->st_ev.get();
@@ -1743,37 +1757,22 @@ int launch_batch(gs_ctx* c, Slot& s, int b, const Slot* before = nullptr, int pr
   HIP_TRY(c, launch_commit(a, st));
   if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
   if (rb != st) HIP_TRY(c, hipStreamWaitEvent(rb, s.ev[4].get(), 0));
-  s.diag_on = diag;
-  s.map_on = diag && map;
-  if (s.map_on && s.rows_in_flight) {   // the rows of the slot's last batch are still being read back (fetch_rows)
+  s.rep = rep;
+  if (rep.rows && s.rows_in_flight) {   // the rows of the slot's last batch are still being read back (fetch_rows)
     HIP_TRY(c, hipStreamWaitEvent(st, s.ev_rows.get(), 0));
     s.rows_in_flight = false;
   }
-  s.top_n = topn;
-  if (diag) {   // behind the commit's write-back, before the next batch's fix-up and commit (stream order)
-    HIP_TRY(c, hipMemsetAsync(s.d_diag.get(), 0, DIAG_BYTES, st));
-    HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));
-    if (rb != st) {
-      HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
-      HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
-    }
-  }
-  if (topn) {   // the same place: the mirror holds the commit's write-back, the slot's score rows are still the batch's
-    HIP_TRY(c, launch_top_scores(top_args(c, s, b), st));
-    if (rb != st) {
-      HIP_TRY(c, hipEventRecord(s.ev_dg.get(), st));
-      HIP_TRY(c, hipStreamWaitEvent(rb, s.ev_dg.get(), 0));
-    }
-  }
+  // behind the commit's write-back, before the next batch's fix-up and commit (stream order): the mirror holds the
+  // commit's write-back, the slot's score rows are still the batch's
+  if (rep.any())
+    if (int rc = launch_reports(c, s, b, st, rb, true)) return rc;
   // Two copies, not one over the adjacent committed words and placements: with one merged copy, 4 processes sharing the
   // GPU (the C4 rehearsal) stalled for 10-100 s at a time, every rank's commit and next eval pass pending;
   // for a direct batch the merged form measured within noise
   HIP_TRY(c, hipMemcpyAsync(s.h_committed.get(), s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, rb));
   HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * b, hipMemcpyDeviceToHost, rb));
-  if (diag)
-    HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * b, hipMemcpyDeviceToHost, rb));
-  if (topn)
-    HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_COUNT_BYTES + TOP_POD_BYTES * b, hipMemcpyDeviceToHost, rb));
+  if (rep.any())
+    if (int rc = read_reports(c, s, b, rb)) return rc;
   HIP_TRY(c, hipEventRecord(s.ev[5].get(), rb));
   return GS_OK;
 }
@@ -1842,11 +1841,9 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     }
     if (M < 0) {
       s.h_out[0] = PlacementDev{-1, (uint32_t)F, 0, 0, GS_PLACED_SLOWPATH, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-      if (s.diag_on) {   // a FitError the host found: nothing landed in the pass, every node from the mirror
-        DiagMapArgs da = diag_args(c, s, b);
-        da.force0 = 1;
-        HIP_TRY(c, launch_wide_pass(s, da, st));
-        HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS, hipMemcpyDeviceToHost, st));
+      if (s.rep.diag) {   // a FitError the host found: nothing landed in the pass, every node from the mirror
+        if (int rc = launch_reports(c, s, b, st, st, false, true)) return rc;
+        if (int rc = read_reports(c, s, 1, st)) return rc;
         HIP_TRY(c, host_wait_stream(st));
       }
       *committed_out = 1;
@@ -1883,20 +1880,16 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     HIP_TRY(c, hipEventRecord(s.ev[3].get(), st));
     HIP_TRY(c, launch_commit(a, st));
     HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
-    if (s.diag_on) HIP_TRY(c, launch_wide_pass(s, diag_args(c, s, b), st));   // (the first pass committed nothing: counters 0)
-    if (s.top_n) HIP_TRY(c, launch_top_scores(top_args(c, s, b), st));         // (... and wrote no table)
+    if (s.rep.any())   // (the first pass committed nothing: the counters are 0, and it wrote no table)
+      if (int rc = launch_reports(c, s, b, st, st, false)) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_committed, s.d_committed.get(), COMMITTED_BYTES, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, host_wait_stream(st));
     c->stats.commit_ms += ev_ms(s.ev[3].get(), s.ev[4].get());
     committed = h_committed[0];
     if (committed < 1) return fail(c, GS_ESTATE, "forced commit made no progress");
     HIP_TRY(c, hipMemcpyAsync(s.h_out, s.d_out, sizeof(PlacementDev) * committed, hipMemcpyDeviceToHost, st));
-    if (s.diag_on)
-      HIP_TRY(c, hipMemcpyAsync(s.h_diag.get(), s.d_diag.get(), sizeof(uint32_t) * DIAG_WORDS * committed,
-                                hipMemcpyDeviceToHost, st));
-    if (s.top_n)
-      HIP_TRY(c, hipMemcpyAsync(s.h_top.get(), s.d_top.get(), TOP_COUNT_BYTES + TOP_POD_BYTES * committed,
-                                hipMemcpyDeviceToHost, st));
+    if (s.rep.any())
+      if (int rc = read_reports(c, s, committed, st)) return rc;
     HIP_TRY(c, host_wait_stream(st));
   }
   flush_exchange_times(c);
@@ -2905,22 +2898,23 @@ void report_host_timing(const gs_ctx* c) {
             c->hx_prep / n, c->hx_flush / n, c->hx_gpu / n, c->hx_reserve / n, (unsigned long long)c->hx_runs,
             c->hx_runs ? c->hx_plain / (double)c->hx_runs : 0.0);
   }
-  if (c->host_timing && c->hd_batches) {
-    const double n = (double)c->hd_batches;
+  const gs_ctx::ReportTiming &hd = c->hr[0], &tp = c->hr[1];
+  if (c->host_timing && hd.batches) {
+    const double n = (double)hd.batches;
     fprintf(stderr, "gpuscore FitError diagnosis, host per batch with such a pod (us, %llu batches, %llu pods, %llu "
             "landed-row versions): deriving the versions %.1f | landed pass, upload to counters %.1f\n",
-            (unsigned long long)c->hd_batches, (unsigned long long)c->hd_pods, (unsigned long long)c->hd_versions,
-            c->hd_derive / n, c->hd_landed / n);
+            (unsigned long long)hd.batches, (unsigned long long)hd.pods, (unsigned long long)hd.versions,
+            hd.derive / n, (hd.landed + hd.merge) / n);
     if (c->hd_map_rows)
       fprintf(stderr, "gpuscore status map: %llu rows read back, %.0f bytes device-to-host per such batch\n",
               (unsigned long long)c->hd_map_rows, (double)c->hd_map_bytes / n);
   }
-  if (c->host_timing && c->tp_batches) {
-    const double n = (double)c->tp_batches;
+  if (c->host_timing && tp.batches) {
+    const double n = (double)tp.batches;
     fprintf(stderr, "gpuscore top scores, host per batch with a scored pod (us, %llu batches, %llu pods, %llu landed-row "
             "versions): deriving the versions %.1f | landed pass, upload to rows %.1f | merge %.1f\n",
-            (unsigned long long)c->tp_batches, (unsigned long long)c->tp_pods, (unsigned long long)c->tp_versions,
-            c->tp_derive / n, c->tp_landed / n, c->tp_merge / n);
+            (unsigned long long)tp.batches, (unsigned long long)tp.pods, (unsigned long long)tp.versions,
+            tp.derive / n, tp.landed / n, tp.merge / n);
   }
 }
 
@@ -3321,12 +3315,7 @@ struct PodRun {
   gs_placement* out = nullptr;
   uint32_t n = 0;
   void* tag = nullptr;
-  gs_fit_diagnosis* diag = nullptr;   // gs_schedule_diag: the FitError diagnosis of each pod (else none is computed)
-  gs_status_map* map = nullptr;       // gs_schedule_diag_nodes: the per-node status rows of those pods (with diag)
-  gs_top_scores* top = nullptr;       // gs_schedule_top_scores: the top-N score table of each scored pod
-  uint32_t topn() const { return top ? top->topn : 0u; }
-  // whether the run's batches run the wide pass with the status rows (a map without rows keeps the counters-only kernels)
-  bool wants_rows() const { return map && map->cap_rows; }
+  Reports rep;
 };
 
 // Several ranks: whether the next run is already known (gs_schedule_submit) is a matter of each rank's timing. The
@@ -3340,6 +3329,219 @@ int agree_next_run(gs_ctx* c, bool* use) {
   std::vector<uint32_t> all(c->nranks);
   if (int rc = exchange_small(c, XSITE_RUNS, nullptr, 4, all.data(), c->sgather ? c->st_ev.get() : c->st.get(), &mine)) return rc;
   for (uint32_t v : all) *use = *use && v;
+  return GS_OK;
+}
+
+// A batch's results as the host applies them: the slot's pinned buffers, or the copy a deferred batch keeps of them
+// (schedule_stream). wide: the wide pass's counters ([pod][DIAG_WORDS]: every node the batch did not land on); top: the
+// device pass's block (per pod the first topn of the nodes the batch did not land on, sorted).
+struct BatchResults {
+  const PlacementDev* out;
+  const PodVec* pods;
+  const uint32_t* wide;
+  const uint8_t* top;
+};
+
+// apply_batch's tables of a reported batch, kept across the batches of a schedule_stream call: the landed nodes, per
+// node its current row version and whether a landing has made it stale, and per pod that wants versions its vector,
+// its index in the batch and its version per landed node; the top scores' merge list.
+struct ReportScratch {
+  std::vector<uint32_t> nodes;
+  std::vector<uint16_t> cur, vidx;
+  std::vector<uint8_t> stale;
+  std::vector<PodVec> pods;
+  std::vector<int> k;
+  std::vector<gs_top_score> rows;
+};
+
+// The status rows of slot sl's batch, just waited for (n committed pods, placements hout), into sl->h_words: the
+// batch's share of the map's rows is chosen here (every batch before it is applied: rows_used is current), and
+// those rows alone are copied, as one block (rows are in queue order), on the landed pass's stream. The batch may be
+// applied deferred, after the batch two ahead is launched into this slot: that batch's wide pass waits for the copy
+// on the device (launch_batch), so the launch is not held back and the rows are not overwritten under the copy.
+int fetch_rows(gs_ctx* c, Slot& sl, const PlacementDev* hout, int n, gs_status_map* mp) {
+  sl.rows_fetched = 0;
+  if (!mp || mp->rows_used >= mp->cap_rows) return GS_OK;
+  uint32_t nfit = 0;
+  for (int k = 0; k < n; ++k) nfit += hout[k].node < 0;
+  const uint32_t nrow = std::min<uint32_t>(nfit, mp->cap_rows - mp->rows_used);
+  if (!nrow) return GS_OK;
+  if (!sl.rep.rows) return fail(c, GS_ESTATE, "status map: the batch ran without its rows");
+  HIP_TRY(c, hipMemcpyAsync(sl.h_words.get(), sl.d_words.get(), sizeof(uint16_t) * (size_t)nrow * c->npad,
+                            hipMemcpyDeviceToHost, c->st_dg.get()));
+  HIP_TRY(c, hipEventRecord(sl.ev_rows.get(), c->st_dg.get()));
+  sl.rows_in_flight = true;
+  sl.rows_fetched = (int)nrow;
+  return GS_OK;
+}
+
+// The diagnoses of the batch's pods with no node (w.k) into dg[0..n): the wide pass's counters plus the landed pass's.
+// mp != nullptr: the first nrow of those pods (queue order) take the map's next rows; their device rows (the wide pass
+// wrote row f for the batch's f-th such pod) are in sl.h_words (fetch_rows), the landed pass's words are patched in at
+// the landed nodes, and each row goes to the caller's words at its stride of num_nodes.
+void merge_diag(gs_ctx* c, const ReportScratch& w, gs_fit_diagnosis* dg, gs_status_map* mp, uint32_t base, int nrow,
+                const Slot& sl, const uint32_t* wide) {
+  const int nL = (int)w.nodes.size();
+  for (int f = 0; f < nrow; ++f) {
+    const uint32_t row = mp->rows_used + (uint32_t)f;
+    uint16_t* dst = mp->words + (size_t)row * c->N;
+    std::memcpy(dst, sl.h_words.get() + (size_t)f * c->npad, sizeof(uint16_t) * c->N);
+    for (int j = 0; j < nL; ++j) dst[w.nodes[j]] = sl.h_lwords.get()[(size_t)f * nL + j];
+    mp->row_of[base + w.k[f]] = (int32_t)row;
+  }
+  if (mp) mp->rows_used += (uint32_t)nrow;
+  const uint32_t* landed = sl.h_ldiag.get();
+  for (size_t f = 0; f < w.k.size(); ++f) {
+    const int k = w.k[f];
+    gs_fit_diagnosis& d = dg[k];
+    d.valid = 1;
+    d.num_all_nodes = c->N;
+    for (int r = 0; r < GS_NUM_FIT_REASONS; ++r) {
+      d.reasons[r] = wide[(size_t)k * DIAG_WORDS + r] + (nL ? landed[f * DIAG_WORDS + r] : 0u);
+      if (fit_reason_status(r) == 2) d.unresolvable_nodes += d.reasons[r];
+    }
+    d.failed_nodes = wide[(size_t)k * DIAG_WORDS + DIAG_FAILED] + (nL ? landed[f * DIAG_WORDS + DIAG_FAILED] : 0u);
+  }
+  if (c->host_timing) {
+    c->hd_map_rows += (uint64_t)nrow;
+    if (nrow) c->hd_map_bytes += sizeof(uint16_t) * ((size_t)nrow * c->npad + w.k.size() * nL);
+  }
+}
+
+// The tables of the batch's scored pods (w.k) into tp's rows and counts from base on: a feasible landed node joins the
+// device's list of the other nodes, which is sorted by (total descending, node ascending) and cut at topn. The top-N of
+// the union lies within the device's top-N of the other nodes and the landed ones.
+int merge_top(gs_ctx* c, ReportScratch& w, gs_top_scores* tp, uint32_t base, const Slot& sl, const uint8_t* topblk) {
+  const int nL = (int)w.nodes.size();
+  const uint32_t* dcnt = reinterpret_cast<const uint32_t*>(topblk);
+  const gs_top_score* drows = reinterpret_cast<const gs_top_score*>(topblk + TOP_COUNT_BYTES);
+  const TopLanded* landed = sl.h_ltop.get();
+  for (size_t f = 0; f < w.k.size(); ++f) {
+    const int k = w.k[f];
+    const uint32_t dn = dcnt[k];
+    if (dn > tp->topn) return fail(c, GS_ESTATE, "top scores: the device pass wrote no table for a scored pod");
+    w.rows.assign(drows + (size_t)k * GS_MAX_TOP_SCORES, drows + (size_t)k * GS_MAX_TOP_SCORES + dn);
+    // (the device's list is full and sorted: a landed node behind its last row cannot make the cut)
+    const bool full = dn == tp->topn;
+    const gs_top_score last = full ? w.rows.back() : gs_top_score{};
+    for (int j = 0; j < nL; ++j) {
+      const TopLanded& l = landed[f * nL + j];
+      if (l.total < 0) continue;
+      if (full && (l.total < last.total || (l.total == last.total && w.nodes[j] > last.node))) continue;
+      gs_top_score r;
+      r.node = w.nodes[j];
+      r.total = l.total;
+      for (int q = 0; q < GS_NUM_PLUGINS; ++q) r.plugin[q] = l.plugin[q];
+      w.rows.push_back(r);
+    }
+    std::sort(w.rows.begin(), w.rows.end(), [](const gs_top_score& a, const gs_top_score& b) {
+      return a.total > b.total || (a.total == b.total && a.node < b.node);
+    });
+    const uint32_t cnt = std::min<uint32_t>((uint32_t)w.rows.size(), tp->topn);
+    std::memcpy(tp->rows + (size_t)(base + k) * tp->topn, w.rows.data(), sizeof(gs_top_score) * cnt);
+    tp->count[base + k] = cnt;
+  }
+  return GS_OK;
+}
+
+// The placements of pods [base, base + n) of `run`, as slot sl's batch committed them (r), to the caller's out[] and
+// the host state, and the run's reports of the batch to their destinations. The device passes behind the commit saw
+// every node the batch did not land on; the landed nodes are added here: walking the placements in queue order, the
+// host state of every node at a pod's turn is its state before that pod's own landing, so at every pod that wants them
+// (the diagnosis: no node; the top scores: placed with more than one node feasible, [upstream] schedulePod skips
+// prioritizeNodes otherwise) the device-format rows of the batch's landed nodes are derived there (derive_row /
+// derive_row_numa, the two gs_debug_mirror_check holds to the device's rows). A row changes only at a landing, so each
+// version is derived once and the pod gets an index per landed node; the landed pass evaluates them on sl's buffers.
+int apply_batch(gs_ctx* c, ReportScratch& w, const PodRun& run, uint32_t base, int n, bool special, Slot& sl,
+                const BatchResults& r) {
+  const gs_pod* pods = run.pods + base;
+  gs_placement* outp = run.out + base;
+  const Reports& rep = run.rep;
+  enum { NONE, NO_NODE, SCORED } want = NONE;   // the pods that want the landed nodes' versions
+  int nrow = 0, nv = 0;
+  if (rep.top) {
+    std::fill_n(rep.top->count + base, n, 0u);
+    want = SCORED;
+  } else if (rep.diag) {
+    std::memset(rep.diag + base, 0, sizeof(gs_fit_diagnosis) * n);
+    if (rep.map) std::fill_n(rep.map->row_of + base, n, -1);
+    int nfit = 0;
+    for (int k = 0; k < n; ++k) nfit += r.out[k].node < 0;
+    if (nfit) want = NO_NODE;
+    if (nfit && rep.map) {
+      nrow = (int)std::min<uint32_t>((uint32_t)nfit, rep.map->cap_rows - rep.map->rows_used);
+      rep.map->rows_dropped += (uint32_t)(nfit - nrow);
+      if (nrow != sl.rows_fetched) return fail(c, GS_ESTATE, "status map: the batch's rows were not read back");
+    }
+  }
+  if (want) {
+    w.nodes.clear();
+    for (int k = 0; k < n; ++k)
+      if (r.out[k].node >= 0 && std::find(w.nodes.begin(), w.nodes.end(), (uint32_t)r.out[k].node) == w.nodes.end())
+        w.nodes.push_back((uint32_t)r.out[k].node);
+    w.cur.assign(w.nodes.size(), 0);
+    w.stale.assign(w.nodes.size(), 1);
+    w.vidx.clear();
+    w.pods.clear();
+    w.k.clear();
+  }
+  const int nL = want ? (int)w.nodes.size() : 0;
+  double t_derive = 0;
+  for (int k = 0; k < n; ++k) {
+    const PlacementDev& pd = r.out[k];
+    gs_placement& o = outp[k];
+    o.node = pd.node;
+    o.feasible = pd.feasible;
+    o.score = pd.node >= 0 ? pd.score : 0;
+    o.ties = pd.node >= 0 ? pd.ties : 0;
+    o.flags = pd.flags & ~PL_INTERNAL_FLAGS;
+    if (pd.flags & GS_PLACED_SLOWPATH) c->stats.slowpath_pods += 1;   // resolved from its whole score row
+    if (want && (want == NO_NODE ? pd.node < 0 : pd.node >= 0 && pd.feasible >= 2)) {
+      const int64_t t0 = c->host_timing ? mono_ns() : 0;
+      for (int j = 0; j < nL; ++j) {
+        if (w.stale[j]) {
+          if (nv >= DIAG_VERSIONS)
+            return fail(c, GS_ESTATE, "%s: landed-row versions overflow", rep.top ? "top scores" : "FitError diagnosis");
+          int64_t* row = reinterpret_cast<int64_t*>(sl.h_dgl.get()) + (size_t)nv * ROW_WORDS;
+          derive_row(c, w.nodes[j], row);
+          derive_row_numa(c, w.nodes[j], row);
+          w.cur[j] = (uint16_t)nv++;
+          w.stale[j] = 0;
+        }
+        w.vidx.push_back(w.cur[j]);
+      }
+      w.pods.push_back(r.pods[k]);
+      w.k.push_back(k);
+      if (c->host_timing) t_derive += (double)(mono_ns() - t0) * 1e-3;
+    }
+    if (int rc = numa_reserve(c, pods[k], r.pods[k], pd)) return rc;
+    apply_placement(c, pods[k], pd.node, special);
+    if (want && pd.node >= 0) w.stale[std::find(w.nodes.begin(), w.nodes.end(), (uint32_t)pd.node) - w.nodes.begin()] = 1;
+  }
+  if (!want || w.k.empty()) return GS_OK;
+  const int64_t t1 = c->host_timing ? mono_ns() : 0;
+  if (nL) {   // (a scored pod landed: the top scores always have one)
+    const Landed kind = rep.top ? Landed::TOP : nrow ? Landed::DIAG_MAP : Landed::DIAG;
+    if (int rc = landed_pass(c, sl, kind, nv, w.pods, w.vidx, nL)) return rc;
+  } else if (nrow) {
+    Where w_(c, "apply_batch: the status rows");
+    HIP_TRY(c, host_wait_stream(c->st_dg.get()));
+  }
+  const int64_t t2 = c->host_timing ? mono_ns() : 0;
+  if (rep.top) {
+    if (int rc = merge_top(c, w, rep.top, base, sl, r.top)) return rc;
+  } else {
+    merge_diag(c, w, rep.diag + base, rep.map, base, nrow, sl, r.wide);
+  }
+  if (c->host_timing) {
+    gs_ctx::ReportTiming& t = c->hr[rep.top ? 1 : 0];
+    t.derive += t_derive;
+    t.landed += (double)(t2 - t1) * 1e-3;
+    t.merge += (double)(mono_ns() - t2) * 1e-3;
+    t.batches += 1;
+    t.versions += nv;
+    t.pods += w.k.size();
+  }
   return GS_OK;
 }
 
@@ -3362,264 +3564,27 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
     (void)host_wait_stream(c->st_ev.get());
     (void)host_wait_stream(c->st_rb.get());   // a voided or in-flight batch's readback into the pinned buffers
   };
-  // dg != nullptr: the batch's FitError diagnoses into dg[0..n). wide: the wide pass's counters of the batch ([pod]
-  // [DIAG_WORDS]: every node the batch did not land on); the landed nodes are added here: walking the placements in
-  // queue order, the host state of every node at a pod with no node is its state at that pod's turn, so the
-  // device-format rows of the batch's landed nodes are derived there (derive_row / derive_row_numa, the two
-  // gs_debug_mirror_check holds to the device's rows) — a row changes only at a landing, so each version is derived
-  // once and the pod gets an index per landed node — and evaluated by the landed pass on slot sl's buffers.
-  // mp != nullptr (with dg): the run's status map, the batch's pods being its pods [base, base + n). The batch's pods
-  // with no node take the map's next rows in queue order while rows are left; their device rows (the wide pass wrote
-  // row f for the batch's f-th such pod) are on their way to sl->h_words (fetch_rows, right after the batch was waited
-  // for, on the landed pass's stream), the landed pass's words are patched in at the landed nodes, and each row goes
-  // to the caller's words at its stride of num_nodes.
-  std::vector<uint32_t> dg_nodes;
-  std::vector<uint16_t> dg_cur, dg_vidx;
-  std::vector<uint8_t> dg_stale;
-  std::vector<PodVec> dg_pods;
-  std::vector<int> dg_k;
-  // The batch's top-N score tables into tp's rows and counts of the run's pods [base, base + n). topblk: the device
-  // pass's block of the batch (per pod the first topn of the nodes the batch did not land on, sorted). The landed
-  // nodes are added here, as the diagnosis adds them: walking the placements in queue order, at every scored pod
-  // (placed, and more than one node feasible: [upstream] schedulePod skips prioritizeNodes otherwise) the host state
-  // of every node is its state at that pod's turn, before its own landing, so the landed nodes' row versions are
-  // derived there and evaluated by the landed pass; a feasible landed node joins the pod's list, which is sorted by
-  // (total descending, node ascending) and cut at topn. The top-N of the union lies within the device's top-N of the
-  // other nodes and the landed ones.
-  std::vector<gs_top_score> tp_rows;
-  auto apply_batch_top = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
-                             bool special, Slot* sl, uint32_t base, gs_top_scores* tp, const uint8_t* topblk) -> int {
-    int nv = 0;
-    dg_nodes.clear();
-    for (int k = 0; k < n; ++k)
-      if (hout[k].node >= 0 && std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)hout[k].node) == dg_nodes.end())
-        dg_nodes.push_back((uint32_t)hout[k].node);
-    const int nL = (int)dg_nodes.size();
-    dg_cur.assign(nL, 0);
-    dg_stale.assign(nL, 1);
-    dg_vidx.clear();
-    dg_pods.clear();
-    dg_k.clear();
-    double t_derive = 0;
-    for (int k = 0; k < n; ++k) {
-      const PlacementDev& pd = hout[k];
-      gs_placement& o = outp[k];
-      o.node = pd.node;
-      o.feasible = pd.feasible;
-      o.score = pd.node >= 0 ? pd.score : 0;
-      o.ties = pd.node >= 0 ? pd.ties : 0;
-      o.flags = pd.flags & ~PL_INTERNAL_FLAGS;
-      if (pd.flags & GS_PLACED_SLOWPATH) c->stats.slowpath_pods += 1;
-      tp->count[base + k] = 0;
-      if (pd.node >= 0 && pd.feasible >= 2) {
-        const int64_t t0 = c->host_timing ? mono_ns() : 0;
-        for (int j = 0; j < nL; ++j) {
-          if (dg_stale[j]) {
-            if (nv >= DIAG_VERSIONS) return fail(c, GS_ESTATE, "top scores: landed-row versions overflow");
-            int64_t* row = reinterpret_cast<int64_t*>(sl->h_dgl.get()) + (size_t)nv * ROW_WORDS;
-            derive_row(c, dg_nodes[j], row);
-            derive_row_numa(c, dg_nodes[j], row);
-            dg_cur[j] = (uint16_t)nv++;
-            dg_stale[j] = 0;
-          }
-          dg_vidx.push_back(dg_cur[j]);
-        }
-        dg_pods.push_back(hpods[k]);
-        dg_k.push_back(k);
-        if (c->host_timing) t_derive += (double)(mono_ns() - t0) * 1e-3;
-      }
-      if (int rc = numa_reserve(c, pods[k], hpods[k], pd)) return rc;
-      apply_placement(c, pods[k], pd.node, special);
-      if (pd.node >= 0) dg_stale[std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)pd.node) - dg_nodes.begin()] = 1;
-    }
-    if (dg_k.empty()) return GS_OK;
-    const int64_t t1 = c->host_timing ? mono_ns() : 0;
-    if (int rc = top_landed(c, *sl, nv, dg_pods, dg_vidx, nL)) return rc;   // (a scored pod landed: nL >= 1)
-    const uint32_t* dcnt = reinterpret_cast<const uint32_t*>(topblk);
-    const gs_top_score* drows = reinterpret_cast<const gs_top_score*>(topblk + TOP_COUNT_BYTES);
-    const TopLanded* landed = sl->h_ltop.get();
-    const int64_t t2 = c->host_timing ? mono_ns() : 0;
-    for (size_t f = 0; f < dg_k.size(); ++f) {
-      const int k = dg_k[f];
-      const uint32_t dn = dcnt[k];
-      if (dn > tp->topn) return fail(c, GS_ESTATE, "top scores: the device pass wrote no table for a scored pod");
-      tp_rows.assign(drows + (size_t)k * GS_MAX_TOP_SCORES, drows + (size_t)k * GS_MAX_TOP_SCORES + dn);
-      // (the device's list is full and sorted: a landed node behind its last row cannot make the cut)
-      const bool full = dn == tp->topn;
-      const gs_top_score last = full ? tp_rows.back() : gs_top_score{};
-      for (int j = 0; j < nL; ++j) {
-        const TopLanded& l = landed[f * nL + j];
-        if (l.total < 0) continue;
-        if (full && (l.total < last.total || (l.total == last.total && dg_nodes[j] > last.node))) continue;
-        gs_top_score r;
-        r.node = dg_nodes[j];
-        r.total = l.total;
-        for (int q = 0; q < GS_NUM_PLUGINS; ++q) r.plugin[q] = l.plugin[q];
-        tp_rows.push_back(r);
-      }
-      std::sort(tp_rows.begin(), tp_rows.end(), [](const gs_top_score& a, const gs_top_score& b) {
-        return a.total > b.total || (a.total == b.total && a.node < b.node);
-      });
-      const uint32_t cnt = std::min<uint32_t>((uint32_t)tp_rows.size(), tp->topn);
-      std::memcpy(tp->rows + (size_t)(base + k) * tp->topn, tp_rows.data(), sizeof(gs_top_score) * cnt);
-      tp->count[base + k] = cnt;
-    }
-    if (c->host_timing) {
-      c->tp_derive += t_derive;
-      c->tp_landed += (double)(t2 - t1) * 1e-3;
-      c->tp_merge += (double)(mono_ns() - t2) * 1e-3;
-      c->tp_batches += 1;
-      c->tp_versions += nv;
-      c->tp_pods += dg_k.size();
-    }
-    return GS_OK;
-  };
-  auto apply_batch = [&](const gs_pod* pods, gs_placement* outp, int n, const PlacementDev* hout, const PodVec* hpods,
-                         bool special, gs_fit_diagnosis* dg = nullptr, const uint32_t* wide = nullptr,
-                         Slot* sl = nullptr, gs_status_map* mp = nullptr, uint32_t base = 0,
-                         gs_top_scores* tp = nullptr, const uint8_t* topblk = nullptr) -> int {
-    if (tp) return apply_batch_top(pods, outp, n, hout, hpods, special, sl, base, tp, topblk);
-    int nfit = 0, nv = 0, nrow = 0;
-    if (mp)
-      for (int k = 0; k < n; ++k) mp->row_of[base + k] = -1;
-    if (dg) {
-      std::memset(dg, 0, sizeof(gs_fit_diagnosis) * n);
-      dg_nodes.clear();
-      for (int k = 0; k < n; ++k) {
-        if (hout[k].node < 0) ++nfit;
-        else if (std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)hout[k].node) == dg_nodes.end())
-          dg_nodes.push_back((uint32_t)hout[k].node);
-      }
-      if (!nfit) dg = nullptr;
-    }
-    if (dg && mp) {
-      nrow = (int)std::min<uint32_t>((uint32_t)nfit, mp->cap_rows - mp->rows_used);
-      mp->rows_dropped += (uint32_t)(nfit - nrow);
-      if (nrow != sl->rows_fetched) return fail(c, GS_ESTATE, "status map: the batch's rows were not read back");
-    }
-    const int nL = dg ? (int)dg_nodes.size() : 0;
-    if (dg) {
-      dg_cur.assign(nL, 0);
-      dg_stale.assign(nL, 1);
-      dg_vidx.clear();
-      dg_pods.clear();
-      dg_k.clear();
-    }
-    double t_derive = 0;
-    for (int k = 0; k < n; ++k) {
-      const PlacementDev& pd = hout[k];
-      gs_placement& o = outp[k];
-      o.node = pd.node;
-      o.feasible = pd.feasible;
-      o.score = pd.node >= 0 ? pd.score : 0;
-      o.ties = pd.node >= 0 ? pd.ties : 0;
-      o.flags = pd.flags & ~PL_INTERNAL_FLAGS;
-      if (pd.flags & GS_PLACED_SLOWPATH) c->stats.slowpath_pods += 1;   // resolved from its whole score row
-      if (dg && pd.node < 0) {
-        const int64_t t0 = c->host_timing ? mono_ns() : 0;
-        for (int j = 0; j < nL; ++j) {
-          if (dg_stale[j]) {
-            if (nv >= DIAG_VERSIONS) return fail(c, GS_ESTATE, "FitError diagnosis: landed-row versions overflow");
-            int64_t* row = reinterpret_cast<int64_t*>(sl->h_dgl.get()) + (size_t)nv * ROW_WORDS;
-            derive_row(c, dg_nodes[j], row);
-            derive_row_numa(c, dg_nodes[j], row);
-            dg_cur[j] = (uint16_t)nv++;
-            dg_stale[j] = 0;
-          }
-          dg_vidx.push_back(dg_cur[j]);
-        }
-        dg_pods.push_back(hpods[k]);
-        dg_k.push_back(k);
-        if (c->host_timing) t_derive += (double)(mono_ns() - t0) * 1e-3;
-      }
-      if (int rc = numa_reserve(c, pods[k], hpods[k], pd)) return rc;
-      apply_placement(c, pods[k], pd.node, special);
-      if (dg && pd.node >= 0)
-        dg_stale[std::find(dg_nodes.begin(), dg_nodes.end(), (uint32_t)pd.node) - dg_nodes.begin()] = 1;
-    }
-    if (!dg) return GS_OK;
-    const int64_t t1 = c->host_timing ? mono_ns() : 0;
-    if (nL) {
-      if (int rc = diag_landed(c, *sl, nv, dg_pods, dg_vidx, nL, nrow > 0)) return rc;
-    } else if (nrow) {
-      Where w_(c, "apply_batch: the status rows");
-      HIP_TRY(c, host_wait_stream(c->st_dg.get()));
-    }
-    for (int f = 0; f < nrow; ++f) {   // (dg_k is in queue order: its first nrow pods hold the rows)
-      const uint32_t row = mp->rows_used + (uint32_t)f;
-      uint16_t* dst = mp->words + (size_t)row * c->N;
-      std::memcpy(dst, sl->h_words.get() + (size_t)f * c->npad, sizeof(uint16_t) * c->N);
-      for (int j = 0; j < nL; ++j) dst[dg_nodes[j]] = sl->h_lwords.get()[(size_t)f * nL + j];
-      mp->row_of[base + dg_k[f]] = (int32_t)row;
-    }
-    if (mp) mp->rows_used += (uint32_t)nrow;
-    const uint32_t* landed = sl->h_ldiag.get();
-    for (size_t f = 0; f < dg_k.size(); ++f) {
-      const int k = dg_k[f];
-      gs_fit_diagnosis& d = dg[k];
-      d.valid = 1;
-      d.num_all_nodes = c->N;
-      for (int r = 0; r < GS_NUM_FIT_REASONS; ++r) {
-        d.reasons[r] = wide[(size_t)k * DIAG_WORDS + r] + (nL ? landed[f * DIAG_WORDS + r] : 0u);
-        if (fit_reason_status(r) == 2) d.unresolvable_nodes += d.reasons[r];
-      }
-      d.failed_nodes = wide[(size_t)k * DIAG_WORDS + DIAG_FAILED] + (nL ? landed[f * DIAG_WORDS + DIAG_FAILED] : 0u);
-    }
-    if (c->host_timing) {
-      c->hd_derive += t_derive;
-      c->hd_landed += (double)(mono_ns() - t1) * 1e-3;
-      c->hd_batches += 1;
-      c->hd_versions += nv;
-      c->hd_pods += dg_k.size();
-      c->hd_map_rows += (uint64_t)nrow;
-      if (nrow) c->hd_map_bytes += sizeof(uint16_t) * ((size_t)nrow * c->npad + (size_t)dg_k.size() * nL);
-    }
-    return GS_OK;
-  };
   // Deferred application: a batch that committed every pod with no host work and no special pod changes no row on
   // the host side (apply_placement / numa_reserve only mirror what the commit wrote to HBM), so its placements are
   // applied to the host state after the batch two ahead is launched — the eval pass then starts right as the previous
   // commit ends instead of after the host's ~0.2 ms of bookkeeping, and runs beside the next commit.
   struct Pend {
-    const gs_pod* pods = nullptr;
-    gs_placement* out = nullptr;
+    PodRun run;             // the batch's run: its pods [base, base + n)
+    uint32_t base = 0;
     int n = 0;
     bool active = false;
-    gs_fit_diagnosis* diag = nullptr;
     Slot* slot = nullptr;   // the slot the batch ran on (its landed-pass buffers)
-    gs_status_map* map = nullptr;
-    uint32_t base = 0;
-    gs_top_scores* top = nullptr;
   } pend;
+  ReportScratch scratch;
   std::vector<uint8_t> pend_top;
   std::vector<PlacementDev> pend_out;
   std::vector<PodVec> pend_pods;
   std::vector<uint32_t> pend_wide;
-  // The status rows of slot sl's batch, just waited for (n committed pods, placements hout), into sl->h_words: the
-  // batch's share of the map's rows is chosen here (every batch before it is applied: rows_used is current), and
-  // those rows alone are copied, as one block (rows are in queue order), on the landed pass's stream. The batch may be
-  // applied deferred, after the batch two ahead is launched into this slot: that batch's wide pass waits for the copy
-  // on the device (launch_batch), so the launch is not held back and the rows are not overwritten under the copy.
-  auto fetch_rows = [&](Slot& sl, const PlacementDev* hout, int n, gs_status_map* mp) -> int {
-    sl.rows_fetched = 0;
-    if (!mp || mp->rows_used >= mp->cap_rows) return GS_OK;
-    uint32_t nfit = 0;
-    for (int k = 0; k < n; ++k) nfit += hout[k].node < 0;
-    const uint32_t nrow = std::min<uint32_t>(nfit, mp->cap_rows - mp->rows_used);
-    if (!nrow) return GS_OK;
-    if (!sl.map_on) return fail(c, GS_ESTATE, "status map: the batch ran without its rows");
-    HIP_TRY(c, hipMemcpyAsync(sl.h_words.get(), sl.d_words.get(), sizeof(uint16_t) * (size_t)nrow * c->npad,
-                              hipMemcpyDeviceToHost, c->st_dg.get()));
-    HIP_TRY(c, hipEventRecord(sl.ev_rows.get(), c->st_dg.get()));
-    sl.rows_in_flight = true;
-    sl.rows_fetched = (int)nrow;
-    return GS_OK;
-  };
   auto apply_pending = [&]() -> int {
     if (!pend.active) return GS_OK;
     pend.active = false;
-    return apply_batch(pend.pods, pend.out, pend.n, pend_out.data(), pend_pods.data(), false, pend.diag,
-                       pend_wide.data(), pend.slot, pend.map, pend.base, pend.top, pend_top.data());
+    return apply_batch(c, scratch, pend.run, pend.base, pend.n, false, *pend.slot,
+                       BatchResults{pend_out.data(), pend_pods.data(), pend_wide.data(), pend_top.data()});
   };
   auto body = [&]() -> int {
     int rc = GS_OK;
@@ -3648,23 +3613,21 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         cur_b = batch_len(c, pods, i, run.n, &cur_special);
         // (a cpuset pod whose node is outside the device cpuset scope ends the batch inside the commit kernel)
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows(), run.topn()))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, run.rep.mode()))) return rc;
       }
       // the batch after this one: in this run, or the first of the next run
       const gs_pod* np = nullptr;
       const uint64_t* ns = nullptr;
       uint32_t nj = 0, nn = 0;
       const uint32_t j = i + cur_b;
-      bool ndiag = run.diag != nullptr;   // whether the batch after this one is diagnosed (its own run's choice)
-      bool nmap = run.wants_rows();
-      uint32_t ntop = run.topn();
+      ReportMode nrep = run.rep.mode();   // the reports of the batch after this one (its own run's choice)
       if (j < run.n) {
         np = pods; ns = run.seq; nj = j; nn = run.n;
       } else {
         if (!have_nxt) have_nxt = next_run(&nxt);
         bool use = have_nxt && nxt.n;
         if (c->nranks > 1 && (rc = agree_next_run(c, &use))) { drain(); return rc; }
-        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; ndiag = nxt.diag != nullptr; nmap = nxt.wants_rows(); ntop = nxt.topn(); }
+        if (use) { np = nxt.pods; ns = nxt.seq; nn = nxt.n; nrep = nxt.rep.mode(); }
       }
       bool spec = false;
       int nb = 0;
@@ -3673,7 +3636,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       double busy = 0;
       if (pend.active && np) {   // the next batch shares a pod uid with the deferred one: its host state first
         const int nb0 = std::min<int>(c->B, (int)(nn - nj));
-        if (uid_overlap(pend.pods, pend.n, np + nj, nb0) && (rc = apply_pending())) { drain(); return rc; }
+        if (uid_overlap(pend.run.pods + pend.base, pend.n, np + nj, nb0) && (rc = apply_pending())) { drain(); return rc; }
       }
       if (can_spec && spec_ok && !cur_special && np && c->dirty_list.empty() && !c->prep_stale) {
         bool sf = false;
@@ -3681,7 +3644,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         if (!sf && !uid_overlap(pods + i, cur_b, np + nj, nb)) {
           rc = stage_batch(c, ahead, np, ns, nj, nb, true);
           const auto t_b = hclk::now();
-          if (!rc) rc = launch_batch(c, ahead, nb, &cur, cur_b, ndiag, nmap, ntop);
+          if (!rc) rc = launch_batch(c, ahead, nb, nrep, &cur, cur_b);
           if (c->host_timing) {
             const double st = std::chrono::duration<double, std::micro>(t_b - t_a).count();
             const double la = std::chrono::duration<double, std::micro>(hclk::now() - t_b).count();
@@ -3704,7 +3667,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         drain();
         if ((rc = apply_pending())) return rc;
         if ((rc = stage_batch(c, cur, pods, run.seq, i, cur_b, false))) return rc;
-        if ((rc = launch_batch(c, cur, cur_b, nullptr, 0, run.diag != nullptr, run.wants_rows(), run.topn()))) return rc;
+        if ((rc = launch_batch(c, cur, cur_b, run.rep.mode()))) return rc;
         inflight = true;
         spec_ok = false;
         continue;
@@ -3713,7 +3676,7 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
       const PodVec* h_pods = cur.h_pods.get();
       // the device-side continuation flag the speculative pass read
       const bool host_work = cur.h_committed.get()[1] != 1;
-      if ((rc = fetch_rows(cur, cur.h_out, committed, run.map))) {
+      if ((rc = fetch_rows(c, cur, cur.h_out, committed, run.rep.map))) {
         if (spec) drain();
         return rc;
       }
@@ -3722,20 +3685,15 @@ int schedule_stream(gs_ctx* c, PodRun run, Next&& next_run, Done&& run_done) {
         // after that batch is launched
         pend_out.assign(cur.h_out, cur.h_out + committed);
         pend_pods.assign(h_pods, h_pods + committed);
-        pend.pods = pods + i;
-        pend.out = run.out + i;
+        pend.run = run;
+        pend.base = i;
         pend.n = committed;
         pend.active = true;
-        pend.diag = run.diag ? run.diag + i : nullptr;
         pend.slot = &cur;
-        pend.map = run.map;
-        pend.base = i;
-        pend.top = run.top;
-        if (run.diag) pend_wide.assign(cur.h_diag.get(), cur.h_diag.get() + (size_t)DIAG_WORDS * committed);
-        if (run.top) pend_top.assign(cur.h_top.get(), cur.h_top.get() + TOP_COUNT_BYTES + TOP_POD_BYTES * committed);
-      } else if ((rc = apply_batch(pods + i, run.out + i, committed, cur.h_out, h_pods, cur_special,
-                                   run.diag ? run.diag + i : nullptr, cur.h_diag.get(), &cur, run.map, i, run.top,
-                                   cur.h_top.get()))) {
+        if (run.rep.diag) pend_wide.assign(cur.h_diag.get(), cur.h_diag.get() + (size_t)DIAG_WORDS * committed);
+        if (run.rep.top) pend_top.assign(cur.h_top.get(), cur.h_top.get() + TOP_COUNT_BYTES + TOP_POD_BYTES * committed);
+      } else if ((rc = apply_batch(c, scratch, run, i, committed, cur_special, cur,
+                                   BatchResults{cur.h_out, h_pods, cur.h_diag.get(), cur.h_top.get()}))) {
         if (spec) drain();
         return rc;
       }
@@ -3803,9 +3761,7 @@ void async_worker(gs_ctx* c) {
       p.pods = r->pods.data();
       p.seq = r->seq.data();
       p.out = r->out;
-      p.diag = r->diag;
-      p.map = r->map;
-      p.top = r->top;
+      p.rep = r->rep;
       p.n = (uint32_t)r->pods.size();
       p.tag = r.get();
       return p;
@@ -3864,16 +3820,7 @@ void async_stop(gs_ctx* c) {
 }  // extern "C++"
 
 namespace {
-// the scope of the FitError diagnosis: one rank, every node checked (the wide pass reads the whole mirror of one
-// rank's commit; under node sampling the reference's map holds only the nodes of the rotation window)
-int diag_supported(gs_ctx* c) {
-  if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "FitError diagnosis: several ranks are not supported");
-  if (c->window_k) return fail(c, GS_EUNSUPPORTED, "FitError diagnosis: node sampling is not supported");
-  return GS_OK;
-}
-
-int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                 gs_fit_diagnosis* diag, gs_status_map* map = nullptr, gs_top_scores* top = nullptr) {
+int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out, Reports rep) {
   int rc = ready(c);
   if (rc) return rc;
   for (uint32_t i = 0; i < npods; ++i)
@@ -3883,15 +3830,13 @@ int schedule_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* 
   run.seq = seq;
   run.out = out;
   run.n = npods;
-  run.diag = diag;
-  run.map = map;
-  run.top = top;
+  run.rep = rep;
   return schedule_stream(c, run, [](PodRun*) { return false; }, [](const PodRun&, int) {});
 }
 
 // gs_schedule_submit: the run copied and queued for the worker
-int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-               gs_fit_diagnosis* diag, uint64_t* ticket, gs_status_map* map = nullptr, gs_top_scores* top = nullptr) {
+int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out, Reports rep,
+               uint64_t* ticket) {
   auto r = std::make_shared<AsyncRun>();
   // checks that write nothing (the worker may be running): on an error, wait for it, then report
   if (c->n_valid != c->N) {
@@ -3910,9 +3855,7 @@ int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* se
   r->seq.resize(npods);
   for (uint32_t i = 0; i < npods; ++i) r->seq[i] = seq ? seq[i] : (uint64_t)i;
   r->out = out;
-  r->diag = diag;
-  r->map = map;
-  r->top = top;
+  r->rep = rep;
   if (!c->aq) {
     c->aq = std::make_unique<AsyncQueue>();
     c->aq->th = std::thread(async_worker, c);
@@ -3932,34 +3875,13 @@ int submit_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* se
 int gs_schedule(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out) {
   if (!c || (npods && (!pods || !out))) return GS_EINVAL;
   quiesce(c);
-  return schedule_run(c, pods, npods, seq, out, nullptr);
-}
-
-int gs_schedule_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                     gs_fit_diagnosis* diag) {
-  if (!c || (npods && (!pods || !out || !diag))) return GS_EINVAL;
-  quiesce(c);
-  if (int rc = diag_supported(c)) return rc;
-  if (int rc = alloc_diag(c)) return rc;
-  return schedule_run(c, pods, npods, seq, out, npods ? diag : nullptr);
+  return schedule_run(c, pods, npods, seq, out, Reports{});
 }
 
 int gs_schedule_submit(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
                        uint64_t* ticket) {
   if (!c || !ticket || (npods && (!pods || !out))) return GS_EINVAL;
-  return submit_run(c, pods, npods, seq, out, nullptr, ticket);
-}
-
-int gs_schedule_submit_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
-                            gs_fit_diagnosis* diag, uint64_t* ticket) {
-  if (!c || !ticket || (npods && (!pods || !out || !diag))) return GS_EINVAL;
-  // (the rank count and the sampling window are fixed before any submission: read beside the worker)
-  if (c->nranks > 1 || c->window_k || !c->st_dg) {
-    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
-    if (int rc = diag_supported(c)) return rc;
-    if (int rc = alloc_diag(c)) return rc;
-  }
-  return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket);
+  return submit_run(c, pods, npods, seq, out, Reports{}, ticket);
 }
 
 namespace {
@@ -3969,63 +3891,69 @@ bool map_begin(gs_status_map* m, uint32_t npods) {
   m->rows_used = m->rows_dropped = 0;
   return true;
 }
+bool top_valid(const gs_top_scores* t) {
+  return t && t->rows && t->count && t->topn >= 1 && t->topn <= GS_MAX_TOP_SCORES;
+}
+
+enum class ReportKind { DIAG, DIAG_NODES, TOP };
+
+// A run with reports of one kind, blocking (ticket == nullptr) or submitted. The scope of the FitError diagnosis is one
+// rank with every node checked (the wide pass reads the whole mirror of one rank's commit; under node sampling the
+// reference's map holds only the nodes of the rotation window), and the top-N score tables share it (the reference then
+// scores only the rotation window). The buffers come with the context's first run of the kind; the status map's and
+// the tables' presuppose the diagnosis' (the landed pass's staged block, slab and stream). A submission runs beside
+// the worker (the rank count and the sampling window are fixed before any submission) and waits for it only for the
+// buffers' first allocation or the refusal's message.
+int report_run(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out, ReportKind kind,
+               Reports rep, bool submit, uint64_t* ticket) {
+  const bool map = kind == ReportKind::DIAG_NODES, top = kind == ReportKind::TOP;
+  if (!c || (submit && !ticket) || (npods && (!pods || !out || (!top && !rep.diag)))) return GS_EINVAL;
+  if ((map && !map_begin(rep.map, npods)) || (top && !top_valid(rep.top))) return GS_EINVAL;
+  const bool allocated = c->st_dg && (!map || c->slot[0].d_words) && (!top || c->slot[0].d_top);
+  if (!submit || c->nranks > 1 || c->window_k || !allocated) {
+    quiesce(c);
+    const char* what = top ? "top scores" : "FitError diagnosis";
+    if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "%s: several ranks are not supported", what);
+    if (c->window_k) return fail(c, GS_EUNSUPPORTED, "%s: node sampling is not supported", what);
+    if (int rc = alloc_diag(c)) return rc;
+    if (map)
+      if (int rc = alloc_map(c)) return rc;
+    if (top)
+      if (int rc = alloc_top(c)) return rc;
+  }
+  if (!npods) rep = Reports{};
+  return submit ? submit_run(c, pods, npods, seq, out, rep, ticket) : schedule_run(c, pods, npods, seq, out, rep);
+}
 }  // namespace
+
+int gs_schedule_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                     gs_fit_diagnosis* diag) {
+  return report_run(c, pods, npods, seq, out, ReportKind::DIAG, Reports{diag, nullptr, nullptr}, false, nullptr);
+}
+
+int gs_schedule_submit_diag(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
+                            gs_fit_diagnosis* diag, uint64_t* ticket) {
+  return report_run(c, pods, npods, seq, out, ReportKind::DIAG, Reports{diag, nullptr, nullptr}, true, ticket);
+}
 
 int gs_schedule_diag_nodes(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
                            gs_fit_diagnosis* diag, gs_status_map* map) {
-  if (!c || (npods && (!pods || !out || !diag)) || !map_begin(map, npods)) return GS_EINVAL;
-  quiesce(c);
-  if (int rc = diag_supported(c)) return rc;
-  if (int rc = alloc_diag(c)) return rc;
-  if (int rc = alloc_map(c)) return rc;
-  return schedule_run(c, pods, npods, seq, out, npods ? diag : nullptr, npods ? map : nullptr);
+  return report_run(c, pods, npods, seq, out, ReportKind::DIAG_NODES, Reports{diag, map, nullptr}, false, nullptr);
 }
 
 int gs_schedule_submit_diag_nodes(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
                                   gs_fit_diagnosis* diag, gs_status_map* map, uint64_t* ticket) {
-  if (!c || !ticket || (npods && (!pods || !out || !diag)) || !map_begin(map, npods)) return GS_EINVAL;
-  if (c->nranks > 1 || c->window_k || !c->st_dg || !c->slot[0].d_words) {
-    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
-    if (int rc = diag_supported(c)) return rc;
-    if (int rc = alloc_diag(c)) return rc;
-    if (int rc = alloc_map(c)) return rc;
-  }
-  return submit_run(c, pods, npods, seq, out, npods ? diag : nullptr, ticket, npods ? map : nullptr);
+  return report_run(c, pods, npods, seq, out, ReportKind::DIAG_NODES, Reports{diag, map, nullptr}, true, ticket);
 }
-
-namespace {
-// the scope of the top-N score tables: that of the diagnosis (under node sampling the reference scores only the
-// rotation window)
-int top_supported(gs_ctx* c) {
-  if (c->nranks > 1) return fail(c, GS_EUNSUPPORTED, "top scores: several ranks are not supported");
-  if (c->window_k) return fail(c, GS_EUNSUPPORTED, "top scores: node sampling is not supported");
-  return GS_OK;
-}
-bool top_valid(const gs_top_scores* t) {
-  return t && t->rows && t->count && t->topn >= 1 && t->topn <= GS_MAX_TOP_SCORES;
-}
-}  // namespace
 
 int gs_schedule_top_scores(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
                            gs_top_scores* top) {
-  if (!c || (npods && (!pods || !out)) || !top_valid(top)) return GS_EINVAL;
-  quiesce(c);
-  if (int rc = top_supported(c)) return rc;
-  if (int rc = alloc_diag(c)) return rc;
-  if (int rc = alloc_top(c)) return rc;
-  return schedule_run(c, pods, npods, seq, out, nullptr, nullptr, npods ? top : nullptr);
+  return report_run(c, pods, npods, seq, out, ReportKind::TOP, Reports{nullptr, nullptr, top}, false, nullptr);
 }
 
 int gs_schedule_submit_top_scores(gs_ctx* c, const gs_pod* pods, uint32_t npods, const uint64_t* seq, gs_placement* out,
                                   gs_top_scores* top, uint64_t* ticket) {
-  if (!c || !ticket || (npods && (!pods || !out)) || !top_valid(top)) return GS_EINVAL;
-  if (c->nranks > 1 || c->window_k || !c->st_dg || !c->slot[0].d_top) {
-    quiesce(c);   // the buffers' first allocation, or the refusal's message: with the worker idle
-    if (int rc = top_supported(c)) return rc;
-    if (int rc = alloc_diag(c)) return rc;
-    if (int rc = alloc_top(c)) return rc;
-  }
-  return submit_run(c, pods, npods, seq, out, nullptr, ticket, nullptr, npods ? top : nullptr);
+  return report_run(c, pods, npods, seq, out, ReportKind::TOP, Reports{nullptr, nullptr, top}, true, ticket);
 }
 
 int gs_status_framework_code(uint16_t word) { return gs_reason_string(GS_STATUS_CODE(word), 0, nullptr, nullptr, 0); }

@@ -11,6 +11,7 @@ import pytest
 
 from koordinator_amd import abi, synth
 from tests import fit_diag_util as fd
+from tests import fit_status_util as fs
 from tests import top_scores_util as tu
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +118,50 @@ def test_chunked_and_submitted():
     e.close()
     for f in range(3):
         assert np.array_equal(np.concatenate([p[f] for p in parts]), np.concatenate([s[f] for s in sub]))
+
+
+@pytest.mark.parametrize("order,topn", [(("top", "nodes", "plain", "diag"), 8), (("diag", "plain", "nodes", "top"), 64)])
+def test_report_kinds_back_to_back(order, topn):
+    """Four submissions of 128 pods, each with another kind of report, waited for only after the last is submitted: the
+    first batch of a run is launched speculatively with that run's reports behind the batch of the run before it, whose
+    placements are applied (deferred) to its own run's destinations. Over the two orders every kind is the batch behind
+    each other kind and the batch in front of one."""
+    c, tt = tu.case(700, 512, 0, False)
+    _, td, st = fs.status_case(700, 512, 0, False)
+    windows = list(range(0, 512, 128))
+    for lo in windows:   # every batch has pods for both landed passes (the oracle alone: 29 / 41 / 27 / 24 pods with no
+        w = slice(lo, lo + 128)   # node, 99 / 87 / 101 / 104 scored pods)
+        assert (tt.placements["node"][w] < 0).sum() >= 1 and (tt.placements["feasible"][w] >= 2).sum() >= 1
+    e = engine(c)
+    # a context's first run of a kind allocates its buffers with the worker idle: empty runs do so before the first
+    # submission, so that none of the four waits for the one before it
+    e.schedule_diag_nodes(c.pods[:0])
+    e.schedule_top_scores(c.pods[:0])
+    submit = {"top": lambda p, s: e.schedule_submit_top_scores(p, s, topn=topn), "nodes": e.schedule_submit_diag_nodes,
+              "plain": e.schedule_submit, "diag": e.schedule_submit_diag}
+    h = [submit[k](c.pods[lo:lo + 128], np.arange(lo, lo + 128, dtype=np.uint64)) for k, lo in zip(order, windows)]
+    res = [e.schedule_wait(x) for x in h]
+    placed = []
+    for k, lo, r in zip(order, windows, res):
+        hi = lo + 128
+        if k == "top":
+            got, rows, count = r
+            tu.check(got, rows, count, tt, topn, lo, hi)
+        elif k == "nodes":
+            got, diag, words, row_of = r
+            fd.check(got, diag, td, c.num_nodes, lo, hi)
+            fs.check_rows(words, row_of, st, lo, hi)
+        elif k == "diag":
+            got, diag = r
+            fd.check(got, diag, td, c.num_nodes, lo, hi)
+        else:
+            got = r
+            for f in ("node", "score", "ties", "feasible"):
+                assert np.array_equal(got[f], tt.placements[f][lo:hi]), f
+        placed.append(got)
+    assert e.mirror_check() == 0
+    e.close()
+    tu.same_placements(np.concatenate(placed), plain_run(700, 512, 0, False)[0])
 
 
 @pytest.mark.parametrize("n,p", [(300, 200), (2100, 200)])
