@@ -1124,6 +1124,43 @@ int gs_debug_mirror_check(gs_ctx* ctx);
 /* Diagnostics: on != 0 makes gs_schedule re-run the host takeCPUs (cpu_accumulator.go:87-232) for every cpuset
  * the commit kernel selected and fail with GS_ESTATE on any difference. */
 int gs_debug_verify_cpuset(gs_ctx* ctx, int on);
+/* Diagnostics: the speculative commit's event counters, summed over the context's life (the numbers gs_destroy prints
+ * for a context created with GS_COMMIT_STAMPS=1 in the environment). Read-only; waits for outstanding submissions.
+ * GS_EINVAL on a context created without that switch (the production kernels count nothing) or with node sampling
+ * (another commit kernel). The selector's counters; with the split selector (one shard, batches of >= 32 pods) the
+ * prep wave makes the first decision of every pod and counts its winner path in the prep_* words. The split_* and
+ * prep_* words are 0 unless a batch ran the split pipeline (split_batches > 0); the est_* words, the single selector's
+ * late-landing estimate, are 0 unless only the single selector ran. The kernel keeps both in the same entries, and the
+ * prep wave is a re-scoring wave under the single selector: a context that ran both pipelines (both counts > 0) has the
+ * estimate added into the four split words and re-scoring job counts into prep_old_path / prep_general_path. */
+typedef struct gs_commit_counters {
+  uint64_t decisions;            /* decisions recorded by the selector, the repeated ones after a rollback included */
+  uint64_t rollbacks;
+  uint64_t rollback_depth;       /* sum over the rollbacks of decided - rolled-back-to pod */
+  uint64_t restored_rows;        /* slots whose row a rollback restored from the undo log */
+  uint64_t full_row;             /* decisions resolved from the pod's whole score row */
+  uint64_t old_path;             /* winner found on the old-nodes-only path (selector) */
+  uint64_t general_path;         /* ... on the general path */
+  uint64_t list_beyond_32;       /* winner / window reached list entry 32 or later */
+  uint64_t list_beyond_64;       /* ... 64 or later: read from list memory, not the header lanes */
+  uint64_t pending_ge;           /* decisions with a pending row whose pre-landing score was >= M */
+  uint64_t pending_ge_rollbacks; /* ... of which rolled back */
+  uint64_t pending_gt;           /* ... > M */
+  uint64_t pending_gt_rollbacks;
+  uint64_t split_late_landings;  /* split selector: landings after the prep wave's snapshot that it applied */
+  uint64_t split_rerecords;      /* ... pods it asked the prep wave to record again over the exact state */
+  uint64_t split_excluded_ties;  /* ... ties of the prep wave's window it excluded */
+  uint64_t split_settled_early;  /* ... pending rows it found settled */
+  uint64_t prep_records;         /* split selector: records of the prep wave (0: only the single selector ran) */
+  uint64_t prep_old_path, prep_general_path, prep_list_beyond_32, prep_list_beyond_64;
+  uint64_t est_decisions;        /* single selector: decisions with a previous pod of the batch placed */
+  uint64_t est_prev_gt;          /* ... whose row, as it stood before its landing, scored > M */
+  uint64_t est_prev_eq;          /* ... == M */
+  uint64_t est_position_moved;   /* ... == M and the tie-break position differs with one more tie */
+  uint64_t split_batches;        /* commit launches that took the split pipeline */
+  uint64_t single_batches;       /* ... the single selector (batches under 32 pods, several ranks) */
+} gs_commit_counters;
+int gs_debug_commit_counters(gs_ctx* ctx, gs_commit_counters* out);
 /* The reference's Filter status for a GS_FAIL_* code of gs_evaluate (codes[]): the first failing plugin in the
  * profile's Filter order (NodeResourcesFit, LoadAwareScheduling, NodeNUMAResource), its message as
  * framework.Status.Message() prints it (the Fit reasons joined by ", ", [upstream] fit.go; load_aware.go:45-46 with

@@ -348,6 +348,14 @@ GS_POD_EVENT_ADD, GS_POD_EVENT_UPDATE, GS_POD_EVENT_DELETE = 0, 1, 2
 GS_EXT_FAIL_DEVICE, GS_EXT_FAIL_RESERVATION, GS_EXT_FAIL_POD = 0x1000, 0x2000, 0x4000
 
 
+# gs_commit_counters (gs_debug_commit_counters): uint64 words in this order
+COMMIT_COUNTER_KEYS = ("decisions", "rollbacks", "rollback_depth", "restored_rows", "full_row", "old_path",
+                       "general_path", "list_beyond_32", "list_beyond_64", "pending_ge", "pending_ge_rollbacks",
+                       "pending_gt", "pending_gt_rollbacks", "split_late_landings", "split_rerecords",
+                       "split_excluded_ties", "split_settled_early", "prep_records", "prep_old_path",
+                       "prep_general_path", "prep_list_beyond_32", "prep_list_beyond_64", "est_decisions", "est_prev_gt",
+                       "est_prev_eq", "est_position_moved", "split_batches", "single_batches")
+
 EXT_ROW_KEYS = ("feasible", "base", "ds_raw", "rs_raw", "total")          # GS_EXT_ROW_*
 EXT_ROWS_RESULT_KEYS = ("node", "score", "ties", "feasible_count", "pref_node", "ds_norm", "rs_norm",
                         "fail_code")                                       # GS_EXT_ROWS_*
@@ -586,6 +594,7 @@ SIGNATURES = {
     "gs_synchronize": (C.c_int, [P]),
     "gs_debug_mirror_check": (C.c_int, [P]),
     "gs_debug_verify_cpuset": (C.c_int, [P, C.c_int]),
+    "gs_debug_commit_counters": (C.c_int, [P, P]),
     "gs_debug_pair_probe": (C.c_int, [P, P, C.c_uint32, P, P, C.c_uint32, C.c_int, P, P]),
     "gs_debug_numa_merge": (C.c_int, [P, P, u32, P]),
     "gs_debug_ext_rows": (C.c_int, [P, P, P, u64, P, P, P]),

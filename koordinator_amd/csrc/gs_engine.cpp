@@ -339,6 +339,7 @@ struct gs_ctx {
   gs_stats stats{};
   DevBuf<uint64_t> d_stamps;      // GS_COMMIT_STAMPS=1: commit-kernel phase cycle sums
   uint64_t stats_all_pods = 0;     // pods placed by gs_schedule over the context's life (stamp averages)
+  uint64_t spec_split_launches = 0, spec_single_launches = 0;   // commit_spec_kernel launches by pipeline (launch_commit_spec's rule)
   // GS_HOST_TIMING=1: host time per batch of schedule_stream, by phase (printed by gs_destroy)
   bool host_timing = false;
   double ht_wait = 0, ht_apply = 0, ht_stage = 0, ht_launch = 0, ht_max_busy = 0;
@@ -527,6 +528,13 @@ int fail(gs_ctx* c, int code, const char* fmt, ...) {
     hipError_t _e = (expr);                                                                 \
     if (_e != hipSuccess) return fail((c), GS_EDEVICE, "%s: %s", #expr, hipGetErrorString(_e)); \
   } while (0)
+
+// diagnostics (gs_debug_commit_counters): which pipeline of commit_spec_kernel a launch takes (launch_commit_spec)
+inline void count_spec_launch(gs_ctx* c, const CommitArgs& a) {
+  if (a.window_k) return;
+  if (a.nranks <= 1 && a.npods >= 32) ++c->spec_split_launches;
+  else ++c->spec_single_launches;
+}
 
 // ---- DefaultEstimator (loadaware/estimator/default_estimator.go:57-108) ------------------------
 int translate(int32_t prio, int r) {   // extension.TranslateResourceNameByPriorityClass
@@ -1754,6 +1762,7 @@ int launch_batch(gs_ctx* c, Slot& s, int b, ReportMode rep, const Slot* before =
   a.prev = prev;
   a.tb_ready = tb_ready;
   ++c->xbatch;
+  count_spec_launch(c, a);
   HIP_TRY(c, launch_commit(a, st));
   if (!untimed) HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
   if (rb != st) HIP_TRY(c, hipStreamWaitEvent(rb, s.ev[4].get(), 0));
@@ -1878,6 +1887,7 @@ int finish_batch(gs_ctx* c, Slot& s, int b, bool clobbered, int* committed_out) 
     a.forced_ties = T;
     a.forced_feasible = (int32_t)F;
     HIP_TRY(c, hipEventRecord(s.ev[3].get(), st));
+    count_spec_launch(c, a);
     HIP_TRY(c, launch_commit(a, st));
     HIP_TRY(c, hipEventRecord(s.ev[4].get(), st));
     if (s.rep.any())   // (the first pass committed nothing: the counters are 0, and it wrote no table)
@@ -3034,6 +3044,8 @@ int gs_destroy(gs_ctx* c) {
   // readbacks into the pinned buffers and the side stream's eval pass may still be in flight
   for (const Stream* s : {&c->st, &c->st_ev, &c->st_rb, &c->st2, &c->st_dg})
     if (*s) (void)host_wait_stream(s->get());
+  // the candidate kernels' stamp pointer is the process's: a later context must not write into this one's buffer
+  if (c->d_stamps) clear_cand_stamps(c->d_stamps.get() + 512);
   delete c;
   return GS_OK;
 }
@@ -4699,6 +4711,29 @@ int gs_debug_numa_merge(gs_ctx* c, const gs_merge_case* cases, uint32_t n, gs_me
   if (e == hipSuccess) e = host_wait_stream(c->st.get());
   if (e == hipSuccess) e = hipMemcpy(out, d_o.get(), sizeof(gs_merge_result) * n, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(c, GS_EDEVICE, "merge probe: %s", hipGetErrorString(e));
+  return GS_OK;
+}
+
+// The speculative commit's event counters (the entries of a.stamps that count events, not cycles: the numbers
+// report_commit_stamps prints): wave 0's region, and the prep wave's (region 1) for the split selector's first decisions.
+int gs_debug_commit_counters(gs_ctx* c, gs_commit_counters* out) {
+  if (!c || !out) return GS_EINVAL;
+  quiesce(c);
+  if (!c->d_stamps || c->window_k) return fail(c, GS_EINVAL, "commit counters: the context was created without GS_COMMIT_STAMPS=1, or with node sampling");
+  std::vector<uint64_t> sa(524);
+  HIP_TRY(c, host_wait_stream(c->st.get()));
+  HIP_TRY(c, hipMemcpy(sa.data(), c->d_stamps.get(), 8 * 524, hipMemcpyDeviceToHost));
+  // entries 47..50 are the split selector's exclusion counts or the single selector's late-landing estimate, and the
+  // prep wave's region is a re-scoring wave's under the single selector: which of them ran is the host's knowledge
+  const bool split = c->spec_split_launches > 0, single = c->spec_single_launches > 0;
+  const uint64_t* w1 = sa.data() + 64;
+  auto sp = [&](uint64_t v) { return split ? v : 0; };
+  auto es = [&](uint64_t v) { return single && !split ? v : 0; };
+  *out = gs_commit_counters{sa[9],      sa[3],      sa[41],     sa[40],     sa[10],     sa[36],     sa[31],
+                            sa[24],     sa[25],     sa[42],     sa[43],     sa[44],     sa[45],     sp(sa[47]),
+                            sp(sa[48]), sp(sa[49]), sp(sa[50]), sp(w1[9]),  sp(w1[36]), sp(w1[31]), sp(w1[24]),
+                            sp(w1[25]), es(sa[47]), es(sa[48]), es(sa[49]), es(sa[50]), c->spec_split_launches,
+                            c->spec_single_launches};
   return GS_OK;
 }
 

@@ -143,6 +143,7 @@ hipError_t launch_patch(const MirrorView& m, const PodVec* pods, int npods, cons
 hipError_t launch_eval_full(const MirrorView& m, const PodVec* pods, int npods, const Profile& pf, uint32_t N,
                             int16_t* scores, uint16_t* codes, int16_t* plugin, int prod_cols, hipStream_t st);
 void set_cand_stamps(uint64_t* p);   // diagnostics: cand_kernel phase cycles (nullptr: off)
+void clear_cand_stamps(const uint64_t* p);   // ... off again if p is the pointer in use (its context is destroyed)
 // lcap: listed nodes per pod (<= LCAP), also the lists' stride
 // The previous batch's landed rows, re-evaluated by cand_kernel's block k for pod k before its histogram (a pass
 // behind a batch whose commit wrote those rows back: the eval pass ran on their state before it); on = 0: none.

@@ -1757,6 +1757,7 @@ static size_t cand_smem_bytes(int max_score) {
 
 static uint64_t* g_cand_stamps = nullptr;
 void set_cand_stamps(uint64_t* p) { g_cand_stamps = p; }
+void clear_cand_stamps(const uint64_t* p) { if (g_cand_stamps == p) g_cand_stamps = nullptr; }
 
 hipError_t launch_fix_levels(int16_t* S, uint32_t ld, int npods, int max_score, int lcap, uint32_t* lists,
                              LevelHdr* hdrs, LevelExt* ext, const CandPatch& cp, hipStream_t st) {

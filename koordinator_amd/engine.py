@@ -551,6 +551,13 @@ class Engine:
             self._chk(rc, "gs_debug_mirror_check")
         return rc
 
+    def commit_counters(self) -> dict:
+        """Diagnostics: the speculative commit's event counters over the engine's life (gs_debug_commit_counters;
+        abi.COMMIT_COUNTER_KEYS). Needs GS_COMMIT_STAMPS=1 in the environment when the engine is created."""
+        out = np.zeros(len(abi.COMMIT_COUNTER_KEYS), np.uint64)
+        self._chk(lib().gs_debug_commit_counters(self._h, abi.ptr(out)), "gs_debug_commit_counters")
+        return {k: int(v) for k, v in zip(abi.COMMIT_COUNTER_KEYS, out)}
+
     def numa_merge(self, cases):
         """Diagnostics: the device's topology-manager Merge on gs_merge_case records (gs_debug_numa_merge)."""
         cases = np.ascontiguousarray(cases, dtype=abi.MERGE_CASE_DTYPE)
